@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: PSF-Attn forward chain throughput (BASELINE.json metric) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-train] [--train-graph] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                    [--full [--no-train] [--train-graph] [--no-cpu-baseline] [--no-extra-legs]]
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs of the last timed step
+(``--dump-outputs DIR``: rank 0's ``DIR/chord_chain_out.npy``, float32, B x N x C — the tensor chord_chain returns; the
+inputs are seeded, so two builds of the library can be compared output for output) and the one JSON line. Everything else
+below — roofline.peak_measured*, cpu_baseline*, train, train_listops, e2e_forward, shapes — runs only with ``--full``
+(``--no-train``, ``--no-cpu-baseline`` and ``--no-extra-legs`` switch legs of it off); without it those fields are null or absent.
 
 ``--gpus N`` with N > 1 started as a plain ``python bench.py`` launches N ranks by itself: the parent process
 (which never touches the GPU) starts ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
@@ -81,9 +88,14 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step as DIR/chord_chain_out.npy (float32, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the measured streaming peaks, the training legs, "
+                         "e2e_forward, shapes and the CPU baselines (each can be switched off by the --no-* options)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--train", dest="train", action="store_true", default=True,
-                    help="also time the data-parallel training leg (default)")
+                    help="with --full: also time the data-parallel training leg (default)")
     ap.add_argument("--no-train", dest="train", action="store_false")
     ap.add_argument("--train-steps", type=int, default=20)
     ap.add_argument("--train-graph", dest="train_graph", action="store_true", default=None,
@@ -92,7 +104,10 @@ def parse_args(argv=None):
                          "processes is where the scaling of a 2.4 ms step is decided — off on one GPU")
     ap.add_argument("--no-train-graph", dest="train_graph", action="store_false")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the e2e_forward and shapes legs (one GPU only)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -376,6 +391,10 @@ def run_rank(args) -> int:
         elapsed = time.perf_counter() - t0
     ev_ms = ev0.elapsed_time(ev1)
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:  # what a caller of chord_chain received from the last timed step (33.5 MB)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "chord_chain_out.npy"), out.detach().float().cpu().numpy())
 
     # which device each rank ran on, as the library's HIP runtime names it: a multi-GPU record must show `world` distinct PCI
     # bus ids (and 8 XCDs / 256 CUs each) — checkable from the line alone
@@ -401,7 +420,7 @@ def run_rank(args) -> int:
     torch.cuda.empty_cache()
 
     bw = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             bw = measured_bandwidth(device)
         except Exception as exc:  # bookkeeping must not lose the headline
@@ -456,7 +475,8 @@ def run_rank(args) -> int:
                                      "peak_measured = 14 steps with a 63 MB W slab each from HBM and the three 33.5 MB V-sized "
                                      "streams re-used step to step (Infinity-Cache resident, as in the chain); "
                                      "peak_measured_hbm_only = every operand beyond the Infinity Cache (2.5 GB footprint); "
-                                     "bytes read + written per second, HIP events, rank 0, outside the timed region",
+                                     "bytes read + written per second, HIP events, rank 0, outside the timed region"
+                                     if bw else None,
                 "frac_of_measured": (achieved / bw["stream_chain_residency"]) if bw and bw.get("stream_chain_residency") else None,
                 "frac_of_measured_hbm_only": (achieved / bw["stream_hbm"]) if bw and bw.get("stream_hbm") else None,
                 # of the step's algorithmic bytes, the part that is re-used within 235 MB of traffic and therefore served by
@@ -479,7 +499,7 @@ def run_rank(args) -> int:
     # line carries it too, as train.rc). If a real multi-GPU run ever trips this, read its records; do not re-run to see it again.
     train = None
     train_listops = None
-    if args.train:
+    if args.full and args.train:
         guard = None
         if world > 1:
             import threading
@@ -504,7 +524,7 @@ def run_rank(args) -> int:
         if world == 1:
             train_listops = listops_leg(args, device)
     e2e, shapes = None, None
-    if world == 1 and rank == 0 and not args.no_extra_legs:
+    if args.full and world == 1 and rank == 0 and not args.no_extra_legs:
         e2e = e2e_forward_leg(device)
         shapes = shapes_leg(device)
 
@@ -517,7 +537,7 @@ def run_rank(args) -> int:
             line["e2e_forward"] = e2e
         if shapes is not None:
             line["shapes"] = shapes
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the GPU side of cfg1 first: its 200 chains are launch-bound, and the CPU legs leave up to 256 OpenMP threads
             # spinning beside the launching thread (one run read 18.7 M tokens/s behind them where it reads 220-250 M alone)
             try:

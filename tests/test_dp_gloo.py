@@ -37,6 +37,7 @@ def _global_batch():
 def _worker(rank, world, port, out_dir):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    torch.cuda.is_available = lambda: False  # a CPU rehearsal on a GPU box too: rank 1 would ask for a second GPU
     r, w, dev = dp.init_from_env(backend="gloo")
     assert (r, w) == (rank, world) and dev.type == "cpu"
     torch.manual_seed(100 + rank)  # replicas start different on purpose ...

@@ -82,7 +82,7 @@ def test_bench_two_rank_rehearsal_replays_the_step_from_a_graph(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PSF_BENCH_REHEARSAL="1")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--train-steps", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--train-steps", "2", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and "rehearsal" in line
@@ -105,7 +105,7 @@ def test_bench_keeps_the_headline_when_a_rank_stalls_in_the_training_leg(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PSF_BENCH_REHEARSAL="1", PSF_BENCH_TEST_STALL_RANK="1", PSF_BENCH_TRAIN_DEADLINE_S="20")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--train-steps", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                          "--train-steps", "2", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode != 0, "a stalled rank must not end as rc 0"
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-2000:]

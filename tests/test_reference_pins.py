@@ -125,6 +125,14 @@ def test_bench_refuses_more_ranks_than_gpus_without_touching_a_gpu():
     assert '{"metric"' not in proc.stdout
 
 
+def test_bench_refuses_zero_timed_steps():
+    """`--steps` is the number of timed steps and ms_per_step is divided by it: zero is an argument error, not a line."""
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"],
+                          capture_output=True, text=True, timeout=300)
+    assert proc.returncode == 2 and "--steps" in proc.stderr
+    assert '{"metric"' not in proc.stdout
+
+
 # ------------------------------------------------------------------------------------------------------------
 # GPU
 # ------------------------------------------------------------------------------------------------------------
@@ -309,7 +317,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu(gpu):
     import json
     env = dict(os.environ, PSF_BENCH_REHEARSAL="1")
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                           "--train-steps", "2", "--train-graph"], capture_output=True, text=True, timeout=600, env=env)
+                           "--train-steps", "2", "--train-graph", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1
@@ -320,6 +328,31 @@ def test_bench_two_rank_rehearsal_on_one_gpu(gpu):
     assert "error" not in tr, tr
     assert tr["global_batch"] == 80 and tr["allreduce_us"] > 0 and tr["allreduce_bytes"] > 4e6 and tr["hip_graph"] == "fwd+bwd"
     assert np.isfinite(tr["loss"]) and tr["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_timed_step(gpu, tmp_path):
+    """A plain `bench.py` run prints the headline line without the legs of --full; --dump-outputs writes the tensor the last
+    timed step returned, checked against the CPU oracle on one batch row of the same seeded inputs."""
+    import json
+
+    import bench
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                           "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "tokens/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert not {"train", "train_listops", "e2e_forward", "shapes", "cpu_baseline", "cpu_baseline_cfg1"} & set(line)
+    got = np.load(tmp_path / "chord_chain_out.npy")
+    assert got.dtype == np.float32 and got.shape == (bench.B_PER_GPU, bench.N_SEQ, bench.C_CH)
+    Ws, V0 = bench.make_inputs(gpu, bench.B_PER_GPU)
+    W = np.stack([w[:1].cpu().numpy() for w in Ws])
+    rows, cols = oc.chord_indices(bench.N_SEQ, bench.L_LINKS)
+    want = oc.chain(np.stack([rows, cols]), W, V0[:1].cpu().numpy(), True)[-1]
+    assert rel_inf(got[:1], want) <= 1e-5
 
 
 # ------------------------------------------------------------------------------------------------------------
