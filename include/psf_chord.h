@@ -63,7 +63,8 @@
 extern "C" {
 #endif
 
-#define PSF_ABI_VERSION 2 /* 2 (round 5): the three "far" training entries are gone, psf_device_info is new, per-step mixer kernels take rows only */
+#define PSF_ABI_VERSION 2 /* 2 (round 5): the three "far" training entries are gone, psf_device_info is new, per-step mixer kernels take rows only.
+                             The bf16 entry points (..._bf16) were added later without a version change: the change is additive. */
 
 #define PSF_MAX_LINKS 64 /* L <= 64: N = 2^63 would need 64 links */
 
@@ -127,6 +128,31 @@ int psf_chord_spmm_fwd_f64(const double* W, const double* V, const double* res, 
                            const int64_t* offsets, void* stream);
 
 /*
+ * bfloat16.  psf_chord_spmm_fwd_bf16, psf_chord_spmm_bwd_bf16, psf_chord_chain_fwd_bf16 and psf_sum_tensors_bf16 take the
+ * arguments of their _f32 twins, in the same order, with the same validation. Every operand and result is bf16, passed as
+ * raw bits (uint16_t: C99 has no bf16 type).
+ *   Storage       W, V, res, out, dZ, dV, dW: bf16.
+ *   Accumulation  each output element is accumulated in f32, in the order of the f32 kernels (links ascending for out and
+ *                 dV, then the residual), and rounded to bf16 exactly once (round to nearest even; a NaN stays a NaN).
+ *                 The product of two bf16 values is exact in f32 whenever it lies in f32's normal range, so the bf16
+ *                 kernels fuse it into the add (one FMA gives the bits of a rounded product followed by a rounded sum);
+ *                 the f32 and f64 kernels never contract. out and dV are therefore bf16_rne(f32 result of the upcast
+ *                 inputs), bit for bit, as long as every nonzero product |W * V| (|W * dZ| for dV) lies in
+ *                 [2^-126, FLT_MAX]. Outside that range the separately rounded product would overflow to infinity or
+ *                 round to the subnormal grid while the fused form keeps it exact, and the result may differ from the
+ *                 f32 reference. dW sums its channels in a per-lane order and is within one bf16 ulp of that.
+ *   Alignment     pointers 2-byte aligned; the 16-byte vector kernels need C % 8 == 0 and 16-byte aligned row operands,
+ *                 anything else runs the generic one-element-per-lane kernel.
+ *   Kernels       forward step and dV: LDS-window kernels (rows of up to 128 channels per chunk), dW: LDS-window
+ *                 kernel (rows of up to 128 channels), the generic kernels otherwise; chain: the per-step launches (no
+ *                 one-launch chain and no fused backward step in bf16).
+ * Not covered: float16, mixed dtypes, the bf16 producer / mixer / flat-head entries and psf_chord_chain_bwd.
+ */
+int psf_chord_spmm_fwd_bf16(const uint16_t* W, const uint16_t* V, const uint16_t* res, uint16_t* out,
+                            int64_t B, int64_t N, int32_t L, int64_t C, int64_t v_batch_stride,
+                            const int64_t* offsets, void* stream);
+
+/*
  * Backward step (spmul_cuda.cu:114-159 backward_host). Either output may be NULL to skip it.
  *   dZ [B,N,C]  gradient w.r.t. the step's output (also the gradient w.r.t. `res`, which is the identity)
  *   W  [B,N,L]  needed for dV;   V [B,N,C] or [N,C] (v_batch_stride == 0) needed for dW
@@ -139,6 +165,9 @@ int psf_chord_spmm_bwd_f32(const float* dZ, const float* W, const float* V, floa
 int psf_chord_spmm_bwd_f64(const double* dZ, const double* W, const double* V, double* dW, double* dV,
                            int64_t B, int64_t N, int32_t L, int64_t C, int64_t v_batch_stride,
                            const int64_t* offsets, void* stream);
+int psf_chord_spmm_bwd_bf16(const uint16_t* dZ, const uint16_t* W, const uint16_t* V, uint16_t* dW, uint16_t* dV,
+                            int64_t B, int64_t N, int32_t L, int64_t C, int64_t v_batch_stride,
+                            const int64_t* offsets, void* stream);
 
 /*
  * Whole forward chain of PSFNet.forward's hot loop (SyntheticExperiments/psf.py:172-188):
@@ -161,6 +190,10 @@ int psf_chord_chain_fwd_f64(const double* const* W_steps, const double* V0, doub
                             int32_t M, int32_t use_residual,
                             int64_t B, int64_t N, int32_t L, int64_t C, int64_t v0_batch_stride,
                             const int64_t* offsets, void* stream);
+int psf_chord_chain_fwd_bf16(const uint16_t* const* W_steps, const uint16_t* V0, uint16_t* const* out_steps,
+                             int32_t M, int32_t use_residual,
+                             int64_t B, int64_t N, int32_t L, int64_t C, int64_t v0_batch_stride,
+                             const int64_t* offsets, void* stream);
 
 /*
  * Whole backward chain of the same loop in one call (SyntheticExperiments/psf.py:172-188 differentiated;
@@ -215,6 +248,8 @@ int psf_linear_wgrad_strided_f32(const float* X, int64_t ldx, const float* dY, i
  *   1 <= count <= 32; n a multiple of 4; every pointer 16-byte aligned; `out` may alias none of the sources.
  */
 int psf_sum_tensors_f32(const float* const* srcs, int32_t count, int64_t n, float* out, void* stream);
+/* bf16 terms, summed left to right in f32 and rounded to bf16 once; n a multiple of 8, other limits as above. */
+int psf_sum_tensors_bf16(const uint16_t* const* srcs, int32_t count, int64_t n, uint16_t* out, void* stream);
 
 /*
  * One Adam step over `count` tensors (the optimizer of the reference's training loop, optim.Adam(net.parameters(), lr),
@@ -494,7 +529,8 @@ int psf_get_tuning(const char* key);
 
 /*
  * Name of the kernel variant the dispatcher would run for this forward shape (for profiles and bench
- * logs; e.g. "chord_fwd_win<f32,L=15,C=8>"). Writes a NUL-terminated string of at most cap-1 chars.
+ * logs; e.g. "chord_fwd_win<f32,L=15,C=8>"). elem_bytes: 2 (bf16), 4 (f32) or 8 (f64). Writes a NUL-terminated string of at
+ * most cap-1 chars.
  */
 int psf_describe_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_bytes,
                      char* buf, int32_t cap);

@@ -34,6 +34,9 @@ SIGNATURES = {
     "psf_chord_spmm_bwd_f64": (_BWD, ctypes.c_int),
     "psf_chord_chain_fwd_f32": (_CHAIN, ctypes.c_int),
     "psf_chord_chain_fwd_f64": (_CHAIN, ctypes.c_int),
+    "psf_chord_spmm_fwd_bf16": (_STEP, ctypes.c_int),
+    "psf_chord_spmm_bwd_bf16": (_BWD, ctypes.c_int),
+    "psf_chord_chain_fwd_bf16": (_CHAIN, ctypes.c_int),
     "psf_chord_chain_bwd_supported": ([c_i64, c_i32, c_i64, c_i32], ctypes.c_int),
     "psf_chord_chain_bwd_f32": ([c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_i32, c_i32,
                                  c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
@@ -43,6 +46,7 @@ SIGNATURES = {
     "psf_adam_step_f32": ([ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), _I64P, c_i32,
                            ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp, c_vp], ctypes.c_int),
     "psf_sum_tensors_f32": ([ctypes.POINTER(c_vp), c_i32, c_i64, c_vp, c_vp], ctypes.c_int),
+    "psf_sum_tensors_bf16": ([ctypes.POINTER(c_vp), c_i32, c_i64, c_vp, c_vp], ctypes.c_int),
     "psf_embed_tokens_f32": ([c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp], ctypes.c_int),
     "psf_affine_rows_f32": ([c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp], ctypes.c_int),
     "psf_embed_tokens_bwd_workspace": ([c_i64, c_i32, c_i32], c_i64),

@@ -98,6 +98,11 @@ def _unit_table():
                       [f"-DPSF_TGS={t}"]))
         units.append((os.path.join(OBJ_DIR, f"bwd_window_tgs{t}.o"), os.path.join(CSRC, "bwd_window_inst.hip"),
                       [f"-DPSF_TGS={t}"]))
+        if t <= 4:  # bf16 forward and dV / dW instances (fwd_window_launch.h: kWinTgsMaxBf16)
+            units.append((os.path.join(OBJ_DIR, f"fwd_window_bf16_tgs{t}.o"), os.path.join(CSRC, "fwd_window_inst.hip"),
+                          [f"-DPSF_TGS={t}", "-DPSF_BF16"]))
+            units.append((os.path.join(OBJ_DIR, f"bwd_window_bf16_tgs{t}.o"), os.path.join(CSRC, "bwd_window_inst.hip"),
+                          [f"-DPSF_TGS={t}", "-DPSF_BF16"]))
     # the forward step that computes its own W tile (fwd_mlp_step_launch.h: kMlpStepTgsMax)
     for t in range(4):
         units.append((os.path.join(OBJ_DIR, f"fwd_mlp_step_tgs{t}.o"), os.path.join(CSRC, "fwd_mlp_step_inst.hip"),

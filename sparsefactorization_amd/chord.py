@@ -24,14 +24,15 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 
-_SUFFIX = {torch.float32: "_f32", torch.float64: "_f64"}
+# bfloat16: bf16 storage, f32 accumulation, one rounding per element (include/psf_chord.h, "bfloat16")
+_SUFFIX = {torch.float32: "_f32", torch.float64: "_f64", torch.bfloat16: "_bf16"}
 
 
 def _suffix(t: torch.Tensor) -> str:
     try:
         return _SUFFIX[t.dtype]
     except KeyError:
-        raise TypeError(f"chord spmm computes in float32 (or float64); got {t.dtype}") from None
+        raise TypeError(f"chord spmm computes in float32, bfloat16 (or float64); got {t.dtype}") from None
 
 
 def _require_hip(*tensors: torch.Tensor) -> torch.device:
@@ -225,16 +226,24 @@ def spmm(index: torch.Tensor, value: torch.Tensor, m: int, n: int, matrix: torch
 # whole chain
 # ----------------------------------------------------------------------------------------------------
 def _sum_tensors(terms: Sequence[torch.Tensor]) -> torch.Tensor:
-    """((t0 + t1) + t2) + ... in one pass (csrc/sum_tensors.hip); all terms fp32, same shape, on one HIP device."""
+    """((t0 + t1) + t2) + ... in one pass (csrc/sum_tensors.hip); all terms fp32 (or all bf16: summed in f32, rounded once),
+    same shape, on one HIP device."""
     dev = _require_hip(*terms)
+    if terms[0].dtype == torch.bfloat16 and (terms[0].numel() % 8 or len(terms) > 32):
+        # outside the kernel's limits (a few elements of odd-sized gradients): the same f32 sum, the same single rounding
+        acc = terms[0].float()
+        for t in terms[1:]:
+            acc.add_(t.float())
+        return acc.to(torch.bfloat16)
     # the kernel reads 16-byte vectors: a contiguous VIEW at a storage offset (an upstream gradient) may be misaligned
     terms = [t.contiguous() for t in terms]
     terms = [t if t.data_ptr() % 16 == 0 else t.clone() for t in terms]
     out = torch.empty_like(terms[0])
     tab = (ctypes.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
+    name = "psf_sum_tensors" + ("_bf16" if out.dtype == torch.bfloat16 else "_f32")
     with torch.cuda.device(dev):
-        rc = _lib.load().psf_sum_tensors_f32(tab, len(terms), out.numel(), out.data_ptr(), _stream_ptr(dev))
-    _lib.check(rc, "psf_sum_tensors_f32")
+        rc = getattr(_lib.load(), name)(tab, len(terms), out.numel(), out.data_ptr(), _stream_ptr(dev))
+    _lib.check(rc, name)
     return out
 
 
@@ -295,6 +304,8 @@ class _ChordChain(torch.autograd.Function):
         # (each is the next step's dZ): they are kept and summed ONCE at the end (psf_sum_tensors_f32) instead of one
         # accumulate kernel per step (14 x 9.5 us per Temporal-Order training step)
         sum_once = ctx.use_residual and need_v0 and g.dtype == torch.float32 and (B * N * C) % 4 == 0 and M + 1 <= 32
+        # bf16: the terms are summed left to right in f32 and rounded once (psf_sum_tensors_bf16), never by a chain of bf16 adds
+        sum_bf16 = ctx.use_residual and need_v0 and g.dtype == torch.bfloat16
         res_terms: List[torch.Tensor] = []
         # everything that is the same for the M launches is looked up once: the small LRA models are bound by the host, and
         # the device guard, the stream object and the symbol look-up of _launch_bwd are most of what a launch costs it
@@ -332,7 +343,7 @@ class _ChordChain(torch.autograd.Function):
             for m in range(M - 1, -1, -1):
                 x_in = V0 if m == 0 else steps[m - 1]
                 stride = stride0 if m == 0 else N * C
-                if sum_once:
+                if sum_once or sum_bf16:
                     res_terms.append(g)
                 elif ctx.use_residual and need_v0:
                     res_acc = g.clone() if res_acc is None else res_acc.add_(g)

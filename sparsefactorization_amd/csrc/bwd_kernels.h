@@ -13,7 +13,8 @@
 namespace psf {
 
 // ------------------------------------------------------------------------------------------------------
-// dV, generic: same thread layout as the generic forward kernel; links ascending, uncontracted mul/add.
+// dV, generic: same thread layout as the generic forward kernel; links ascending, uncontracted mul/add (bf16: f32
+// accumulator, exact products fused, one rounding at the store).
 // ------------------------------------------------------------------------------------------------------
 template <typename T, int VEC>
 __global__ void __launch_bounds__(kBlock)
@@ -31,9 +32,9 @@ chord_dv_generic_k(const T* __restrict__ dZ, const T* __restrict__ W, T* __restr
   const T* __restrict__ Wb = W + (int64_t)b * gm.N * gm.L;
   const T* __restrict__ Zb = dZ + (int64_t)b * gm.N * gm.C + (int64_t)cg * VEC;
 
-  Vec<T, VEC> acc;
+  Vec<Acc<T>, VEC> acc;
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) acc.e[i] = T(0);
+  for (int i = 0; i < VEC; ++i) acc.e[i] = Acc<T>(0);
 
 #pragma unroll 4
   for (int k = 0; k < gm.L; ++k) {
@@ -43,7 +44,7 @@ chord_dv_generic_k(const T* __restrict__ dZ, const T* __restrict__ W, T* __restr
     const Vec<T, VEC> x = ld<T, VEC>(Zb + (int64_t)src * gm.C);
     axpy_rn<T, VEC>(acc, w, x);
   }
-  st<T, VEC>(dV + ((int64_t)b * gm.N + q) * gm.C + (int64_t)cg * VEC, acc);
+  st<T, VEC>(dV + ((int64_t)b * gm.N + q) * gm.C + (int64_t)cg * VEC, narrow<T, VEC>(acc));
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -74,15 +75,15 @@ chord_dw_generic_k(const T* __restrict__ dZ, const T* __restrict__ V, T* __restr
     int src = pc + offs.v[k];
     if (src >= gm.N) src -= gm.N;
     const T* __restrict__ Vrow = Vb + (int64_t)src * gm.C;
-    T part = T(0);
+    Acc<T> part = Acc<T>(0);
     for (int cg = g; cg < gm.CG; cg += TG) {
       const Vec<T, VEC> z = ld<T, VEC>(Zrow + (int64_t)cg * VEC);
       const Vec<T, VEC> x = ld<T, VEC>(Vrow + (int64_t)cg * VEC);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) part = add_rn(part, mul_rn(z.e[i], x.e[i]));
+      for (int i = 0; i < VEC; ++i) part = madd_rn<T>(part, z.e[i], x.e[i]);
     }
     for (int s = TG >> 1; s > 0; s >>= 1) part = add_rn(part, __shfl_xor(part, s, 64));
-    if (g == 0 && row_ok) dWrow[k] = part;
+    if (g == 0 && row_ok) dWrow[k] = (T)part;
   }
 }
 

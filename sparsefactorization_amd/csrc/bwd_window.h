@@ -19,6 +19,9 @@
 //       column k of the far W tile (a 4-byte load with a 60-byte lane stride: the one place where a row-major
 //       W costs L2->L1 bandwidth; a k-major W from the producer would remove it — DESIGN.md §4.3).
 //       Links ascending with uncontracted mul/add: bit-identical to the oracle.
+//
+// bf16 (T = __bf16, bwd_window_inst.hip with -DPSF_BF16): 16-byte groups of 8 channels, f32 accumulation (Acc<T>), one
+// rounding per element — dV stays bit-identical to bf16_rne of the f32 oracle; dW rounds its f32 row dot once.
 #pragma once
 
 #include "fwd_window.h"
@@ -152,20 +155,20 @@ chord_dw_win_k(const T* __restrict__ dZ, const T* __restrict__ V, T* __restrict_
       V4 x;
       if (k < KN) x = sWin[((pl + chord_off(k)) << TGS) + g];
       else x = far[j][k - KN < NF ? k - KN : 0];
-      T part = T(0);
+      Acc<T> part = Acc<T>(0);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) part = add_rn(part, mul_rn(dz[j].e[i], x.e[i]));
+      for (int i = 0; i < VEC; ++i) part = madd_rn<T>(part, dz[j].e[i], x.e[i]);
       // Lanes past the last channel group add nothing — by a select, not by a zero factor: their window slots were never
       // staged, and whatever an earlier kernel left in that LDS (a NaN or Inf pattern) times zero is NaN. (Until round 5 this
       // zeroed dz instead: dW rows came out NaN once in a while for C / 4 not a power of two, depending on what had run before.)
-      if constexpr (EDGE) part = cg_ok ? part : T(0);
-      if constexpr (sizeof(T) == 4) {
+      if constexpr (EDGE) part = cg_ok ? part : Acc<T>(0);
+      if constexpr (__is_same(Acc<T>, float)) {  // f32, and bf16 (f32 partial sums)
         part = row_group_sum<TG>(part);
       } else {
 #pragma unroll
         for (int s = TG >> 1; s > 0; s >>= 1) part = add_rn(part, __shfl_xor(part, s, 64));
       }
-      if (g == 0) sOutF[mis + pl * L + k] = part;
+      if (g == 0) sOutF[mis + pl * L + k] = (T)part;  // (bf16: the one rounding of the element)
     }
   }
   __syncthreads();
@@ -261,9 +264,9 @@ chord_dv_win_k(const T* __restrict__ dZ, const T* __restrict__ W, T* __restrict_
   for (int j = 0; j < R; ++j) {
     const int pl = j * RS + rs;
     const int q = q0 + pl;
-    V4 acc;
+    Vec<Acc<T>, VEC> acc;
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) acc.e[i] = T(0);
+    for (int i = 0; i < VEC; ++i) acc.e[i] = Acc<T>(0);
 #pragma unroll
     for (int k = 0; k < KN; ++k) {
       const int wr = TR + pl - chord_off(k);  // in [0, 2TR): near offsets are <= TR
@@ -275,7 +278,11 @@ chord_dv_win_k(const T* __restrict__ dZ, const T* __restrict__ W, T* __restrict_
     // (Non-temporal dV / dW stores for rows of >= 64 channels: 4-7 % per step with rotating operands, -1 % in the ListOps
     // training step where the next kernel reads this dV at once; the dW tile alone non-temporal, as in the fused step:
     // +0.1 % there — profiles/r05x_bwd_wide_nt_ab.log, r05x_lra_step_nt_ab.log, r05x_step_wide_dw_nt_ab.log. Not taken.)
-    if (!EDGE || (q < N && cg_ok)) st<T, VEC>(dV + ((int64_t)b * N + q) * C + (int64_t)cg * VEC, acc);
+    if (!EDGE || (q < N && cg_ok)) {
+      // (f32 / f64 store the accumulator itself: the identity narrow() let hipcc reorder packed-multiply operands here)
+      if constexpr (__is_same(Acc<T>, T)) st<T, VEC>(dV + ((int64_t)b * N + q) * C + (int64_t)cg * VEC, acc);
+      else st<T, VEC>(dV + ((int64_t)b * N + q) * C + (int64_t)cg * VEC, narrow<T, VEC>(acc));
+    }
   }
 }
 

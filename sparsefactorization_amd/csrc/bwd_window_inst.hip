@@ -1,5 +1,6 @@
 // bwd_window_inst.hip — instantiates the LDS-window backward kernels for ONE (channel-group shift, workgroup
-// size) pair. Built once per compiled pair (-DPSF_TGS=0..6 [-DPSF_NT=1024]); see build.py.
+// size) pair. Built once per compiled pair (-DPSF_TGS=0..6 [-DPSF_NT=1024]); see build.py. With -DPSF_BF16 the unit holds
+// the bf16 dV / dW instances of that TGS instead (NT 256: dW R 1, dV R 2).
 #ifndef PSF_TGS
 #error "compile with -DPSF_TGS=<0..6>"
 #endif
@@ -27,10 +28,10 @@ hipError_t raise_lds_limit(K kern, int bytes, std::atomic<int>& done) {
   return hipSuccess;
 }
 
-template <int L, int TGS, int R, int NT, bool EDGE>
-hipError_t launch_dw(const BwdWinArgs& a) {
-  using Cfg = BwdWinCfg<float, L, TGS, R, NT>;
-  auto kern = chord_dw_win_k<float, L, TGS, R, NT, EDGE>;
+template <typename T, int L, int TGS, int R, int NT, bool EDGE>
+hipError_t launch_dw(const BwdWinArgsT<T>& a) {
+  using Cfg = BwdWinCfg<T, L, TGS, R, NT>;
+  auto kern = chord_dw_win_k<T, L, TGS, R, NT, EDGE>;
   static std::atomic<int> done{0};
   if (hipError_t e = raise_lds_limit(kern, Cfg::lds_dw, done); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(NT), Cfg::lds_dw, a.stream, a.dZ, a.WV, a.out, a.gm, a.offs,
@@ -38,10 +39,10 @@ hipError_t launch_dw(const BwdWinArgs& a) {
   return hipGetLastError();
 }
 
-template <int L, int TGS, int R, int NT, bool EDGE>
-hipError_t launch_dv(const BwdWinArgs& a) {
-  using Cfg = BwdWinCfg<float, L, TGS, R, NT>;
-  auto kern = chord_dv_win_k<float, L, TGS, R, NT, EDGE>;
+template <typename T, int L, int TGS, int R, int NT, bool EDGE>
+hipError_t launch_dv(const BwdWinArgsT<T>& a) {
+  using Cfg = BwdWinCfg<T, L, TGS, R, NT>;
+  auto kern = chord_dv_win_k<T, L, TGS, R, NT, EDGE>;
   static std::atomic<int> done{0};
   if (hipError_t e = raise_lds_limit(kern, Cfg::lds_dv, done); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(NT), Cfg::lds_dv, a.stream, a.dZ, a.WV, a.out, a.gm, a.offs,
@@ -75,13 +76,13 @@ hipError_t launch_dwc_L(int L, const BwdWinArgs& a) {
   }
 }
 
-template <int TGS, int R, int NT, bool DW>
-hipError_t launch_L(int L, const BwdWinArgs& a) {
+template <int TGS, int R, int NT, bool DW, typename T = float>
+hipError_t launch_L(int L, const BwdWinArgsT<T>& a) {
   switch (L) {
-#define PSF_CASE(LL)                                                                                            \
-  case LL:                                                                                                      \
-    if constexpr (DW) return a.edge ? launch_dw<LL, TGS, R, NT, true>(a) : launch_dw<LL, TGS, R, NT, false>(a); \
-    else return a.edge ? launch_dv<LL, TGS, R, NT, true>(a) : launch_dv<LL, TGS, R, NT, false>(a);
+#define PSF_CASE(LL)                                                                                                  \
+  case LL:                                                                                                            \
+    if constexpr (DW) return a.edge ? launch_dw<T, LL, TGS, R, NT, true>(a) : launch_dw<T, LL, TGS, R, NT, false>(a); \
+    else return a.edge ? launch_dv<T, LL, TGS, R, NT, true>(a) : launch_dv<T, LL, TGS, R, NT, false>(a);
     PSF_CASE(4) PSF_CASE(5) PSF_CASE(6) PSF_CASE(7) PSF_CASE(8) PSF_CASE(9) PSF_CASE(10) PSF_CASE(11)
     PSF_CASE(12) PSF_CASE(13) PSF_CASE(14) PSF_CASE(15) PSF_CASE(16) PSF_CASE(17) PSF_CASE(18)
     PSF_CASE(19) PSF_CASE(20)
@@ -93,6 +94,19 @@ hipError_t launch_L(int L, const BwdWinArgs& a) {
 
 }  // namespace
 
+#ifdef PSF_BF16
+static_assert(PSF_NT == 256 && PSF_TGS <= kWinTgsMaxBf16, "bf16 backward instances: NT 256, TGS 0..kWinTgsMaxBf16");
+template <int TGS>
+hipError_t launch_dw_win_bf16(int L, const BwdWinArgsT<__bf16>& a) {
+  return launch_L<TGS, 1, 256, true, __bf16>(L, a);
+}
+template <int TGS>
+hipError_t launch_dv_win_bf16(int L, const BwdWinArgsT<__bf16>& a) {
+  return launch_L<TGS, 2, 256, false, __bf16>(L, a);
+}
+template hipError_t launch_dw_win_bf16<PSF_TGS>(int L, const BwdWinArgsT<__bf16>& a);
+template hipError_t launch_dv_win_bf16<PSF_TGS>(int L, const BwdWinArgsT<__bf16>& a);
+#else
 #if PSF_NT == 256
 template <int TGS>
 hipError_t launch_dw_win(int rows, int L, const BwdWinArgs& a) {
@@ -206,5 +220,6 @@ hipError_t launch_bwd_fused_edge(int L, const BwdWinArgs& a) {
 }
 template hipError_t launch_bwd_fused_edge<PSF_TGS>(int L, const BwdWinArgs& a);
 #endif
+#endif  // PSF_BF16
 
 }  // namespace psf

@@ -8,23 +8,32 @@
 
 namespace psf {
 
-struct BwdWinArgs {
-  const float* dZ;
-  const float* WV;  // dV: W [B,N,L];  dW: V [B or 1,N,C]
-  float* out;       // dV: dV [B,N,C]; dW: dW [B,N,L]
+template <typename T>
+struct BwdWinArgsT {
+  const T* dZ;
+  const T* WV;  // dV: W [B,N,L];  dW: V [B or 1,N,C]
+  T* out;       // dV: dV [B,N,C]; dW: dW [B,N,L]
   Geom gm;
   Offsets offs;
   int64_t w_total;  // B*N*L
   bool edge;
   hipStream_t stream;
-  const float* V2 = nullptr;    // fused step (bwd_fused.h): WV = W, V2 = V, out = dV, out2 = dW
-  float* out2 = nullptr;
+  const T* V2 = nullptr;    // fused step (bwd_fused.h): WV = W, V2 = V, out = dV, out2 = dW
+  T* out2 = nullptr;
   int ablate = 0;               // fused step, diagnostic builds only (bwd_fused.h: ABL)
   int wg_per_cu = 0;            // fused step: 0 = whatever fits; n > 0: at most n workgroups per CU (by requesting more LDS)
 };
 
+using BwdWinArgs = BwdWinArgsT<float>;
+
 template <int TGS>
 hipError_t launch_dw_win(int rows, int L, const BwdWinArgs& a);
+// bf16 instances (bwd_window_inst.hip built with -DPSF_BF16): dW 256 threads x 1 row, dV 256 threads x 2 rows, TGS 0..4
+// (fwd_window_launch.h: kWinTgsMaxBf16); rows of up to 128 channels for dW, 128-channel chunks for dV
+template <int TGS>
+hipError_t launch_dw_win_bf16(int L, const BwdWinArgsT<__bf16>& a);
+template <int TGS>
+hipError_t launch_dv_win_bf16(int L, const BwdWinArgsT<__bf16>& a);
 // chunk-looping dW (bwd_dw_chunk.h) for rows of >= 32 channels: 8 or 16 lanes per row chunk (TGS 3 / 4), 256 threads,
 // one row per thread. r02 sweep (profiles/r02c_dw_sweep*.log, us per launch at ListOps N=2000 C=128 / genome C=32):
 // TG=8 R=1 21.0 (15.3 in one launch) / 20.6; TG=16 R=1 15.2 / 20.7; R=2 25.5 / 24.8; 1024 threads x 1 row 28.2 / 33.5;

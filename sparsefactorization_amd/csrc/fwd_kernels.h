@@ -17,7 +17,8 @@
 
 namespace psf {
 
-// Any N, any L <= 64, any C (VEC = 1 when C is not a multiple of the 16-byte vector width), any offsets.
+// Any N, any L <= 64, any C (VEC = 1 when C is not a multiple of the 16-byte vector width), any offsets. f32, f64 and bf16
+// (bf16 accumulates in f32: Acc<T>, psf_common.h).
 // Thread (r, g) owns VEC channels of one row and walks the links in order; the TG lanes of a row read the
 // same W element (a wave-level broadcast).
 template <typename T, int VEC>
@@ -36,9 +37,9 @@ chord_fwd_generic_k(const T* __restrict__ W, const T* __restrict__ V, const T* _
   const T* __restrict__ Wrow = W + ((int64_t)b * gm.N + p) * gm.L;
   const T* __restrict__ Vb = V + (int64_t)b * gm.v_bstride + (int64_t)cg * VEC;
 
-  Vec<T, VEC> acc;
+  Vec<Acc<T>, VEC> acc;
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) acc.e[i] = T(0);
+  for (int i = 0; i < VEC; ++i) acc.e[i] = Acc<T>(0);
 
 #pragma unroll 4
   for (int k = 0; k < gm.L; ++k) {
@@ -51,11 +52,11 @@ chord_fwd_generic_k(const T* __restrict__ W, const T* __restrict__ V, const T* _
 
   const int64_t o = ((int64_t)b * gm.N + p) * gm.C + (int64_t)cg * VEC;
   if (res != nullptr) {
-    const Vec<T, VEC> rv = ld<T, VEC>(res + o);
+    const Vec<Acc<T>, VEC> rv = widen<T, VEC>(ld<T, VEC>(res + o));
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc.e[i] = add_rn(acc.e[i], rv.e[i]);
   }
-  st<T, VEC>(out + o, acc);
+  st<T, VEC>(out + o, narrow<T, VEC>(acc));
 }
 
 }  // namespace psf

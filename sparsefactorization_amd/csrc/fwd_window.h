@@ -24,6 +24,10 @@
 //
 // Per output row this moves (2 + L-KN) V rows through the L2->CU path instead of L and keeps the accumulation
 // order of the generic kernel, so both agree bit for bit. Requires N >= 2*TR (the window wraps at most once).
+//
+// bf16 (T = __bf16): a 16-byte group is 8 channels, so at C = 8 a row is one group (TGS = 0) and a tile has twice the rows
+// of the f32 tile at the same NT and R (512 at NT 256, R 2: KN = 11 near links against 10). W rows are L*2 bytes, staged by
+// the same 16-byte chunks. Accumulation is in f32 (Acc<T>), each element rounded to bf16 once at the store.
 #pragma once
 
 #include "psf_common.h"
@@ -218,9 +222,9 @@ __device__ __forceinline__ void fwd_win_body(const T* __restrict__ W, const T* _
   for (int j = 0; j < R; ++j) {
     const int pl = j * RS + rs;
     const int p = p0 + pl;
-    V4 acc;
+    Vec<Acc<T>, VEC> acc;
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) acc.e[i] = T(0);
+    for (int i = 0; i < VEC; ++i) acc.e[i] = Acc<T>(0);
     const T* __restrict__ wrow = sWf + (ALIGNED ? 0 : mis) + pl * L;
 #pragma unroll
     for (int k = 0; k < KN; ++k) {
@@ -230,14 +234,16 @@ __device__ __forceinline__ void fwd_win_body(const T* __restrict__ W, const T* _
 #pragma unroll
     for (int f = 0; f < NF; ++f) axpy_rn<T, VEC>(acc, wrow[KN + f], far[j][f]);
     if constexpr (RES) {
+      const Vec<Acc<T>, VEC> rw = widen<T, VEC>(rres[j]);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) acc.e[i] = add_rn(acc.e[i], rres[j].e[i]);
+      for (int i = 0; i < VEC; ++i) acc.e[i] = add_rn(acc.e[i], rw.e[i]);
     }
+    const V4 o = narrow<T, VEC>(acc);  // (bf16: the one rounding of the element)
     if constexpr (ALIGNED) {
       PSF_GLOBAL char* ob = sbase(reinterpret_cast<char*>(out + ((int64_t)b * N + p0) * C));
-      stg<T, VEC>(ob + lane_off((uint32_t)pl * ((uint32_t)C * (uint32_t)sizeof(T)) + (uint32_t)cg * 16u), acc);
+      stg<T, VEC>(ob + lane_off((uint32_t)pl * ((uint32_t)C * (uint32_t)sizeof(T)) + (uint32_t)cg * 16u), o);
     } else {
-      if (!EDGE || (p < N && cg_ok)) st<T, VEC>(out + ((int64_t)b * N + p) * C + (int64_t)cg * VEC, acc);  // full tiles: no predicate
+      if (!EDGE || (p < N && cg_ok)) st<T, VEC>(out + ((int64_t)b * N + p) * C + (int64_t)cg * VEC, o);  // full tiles: no predicate
     }
   }
 }

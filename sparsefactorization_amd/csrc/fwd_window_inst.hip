@@ -1,6 +1,6 @@
 // fwd_window_inst.hip — instantiates the LDS-window forward kernels for ONE (channel-group shift, workgroup
 // size) pair. Built once per compiled pair (-DPSF_TGS=0..6 [-DPSF_NT=1024]) so the instances compile in
-// parallel; see build.py.
+// parallel; see build.py. With -DPSF_BF16 the unit holds the bf16 instances of that TGS instead (NT 256, R 2 only).
 #ifndef PSF_TGS
 #error "compile with -DPSF_TGS=<0..6>"
 #endif
@@ -16,10 +16,10 @@
 namespace psf {
 namespace {
 
-template <int L, int TGS, int R, int NT, bool RES, int MODE>
-hipError_t launch_one(const FwdWinArgs& a) {
-  using Cfg = FwdWinCfg<float, L, TGS, R, NT>;
-  auto kern = chord_fwd_win_k<float, L, TGS, R, NT, /*DMA=*/true, RES, MODE>;
+template <typename T, int L, int TGS, int R, int NT, bool RES, int MODE>
+hipError_t launch_one(const FwdWinArgsT<T>& a) {
+  using Cfg = FwdWinCfg<T, L, TGS, R, NT>;
+  auto kern = chord_fwd_win_k<T, L, TGS, R, NT, /*DMA=*/true, RES, MODE>;
   // Occupancy limiter: a CU takes floor(160 KB / LDS per workgroup) workgroups, so asking for just over
   // 160 KB / (n + 1) caps it at n. (cfg2: 3 per CU is 2-3 % faster than the 4 the registers allow — fewer
   // windows competing for the XCD's L2; 2 per CU is 10 % slower. DESIGN.md §4.1.)
@@ -42,21 +42,21 @@ hipError_t launch_one(const FwdWinArgs& a) {
   return hipGetLastError();
 }
 
-template <int L, int TGS, int R, int NT>
-hipError_t launch_flags(const FwdWinArgs& a) {
+template <typename T, int L, int TGS, int R, int NT>
+hipError_t launch_flags(const FwdWinArgsT<T>& a) {
   if (a.res != nullptr)
-    return a.edge ? launch_one<L, TGS, R, NT, true, 1>(a)
-                  : (a.gm.aligned ? launch_one<L, TGS, R, NT, true, 2>(a) : launch_one<L, TGS, R, NT, true, 0>(a));
-  return a.edge ? launch_one<L, TGS, R, NT, false, 1>(a)
-                : (a.gm.aligned ? launch_one<L, TGS, R, NT, false, 2>(a) : launch_one<L, TGS, R, NT, false, 0>(a));
+    return a.edge ? launch_one<T, L, TGS, R, NT, true, 1>(a)
+                  : (a.gm.aligned ? launch_one<T, L, TGS, R, NT, true, 2>(a) : launch_one<T, L, TGS, R, NT, true, 0>(a));
+  return a.edge ? launch_one<T, L, TGS, R, NT, false, 1>(a)
+                : (a.gm.aligned ? launch_one<T, L, TGS, R, NT, false, 2>(a) : launch_one<T, L, TGS, R, NT, false, 0>(a));
 }
 
-template <int TGS, int R, int NT>
-hipError_t launch_L(int L, const FwdWinArgs& a) {
+template <typename T, int TGS, int R, int NT>
+hipError_t launch_L(int L, const FwdWinArgsT<T>& a) {
   switch (L) {
 #define PSF_CASE(LL) \
   case LL:           \
-    return launch_flags<LL, TGS, R, NT>(a);
+    return launch_flags<T, LL, TGS, R, NT>(a);
     PSF_CASE(4) PSF_CASE(5) PSF_CASE(6) PSF_CASE(7) PSF_CASE(8) PSF_CASE(9) PSF_CASE(10) PSF_CASE(11)
     PSF_CASE(12) PSF_CASE(13) PSF_CASE(14) PSF_CASE(15) PSF_CASE(16) PSF_CASE(17) PSF_CASE(18)
     PSF_CASE(19) PSF_CASE(20)
@@ -68,17 +68,29 @@ hipError_t launch_L(int L, const FwdWinArgs& a) {
 
 }  // namespace
 
+#ifdef PSF_BF16
+template <int TGS>
+hipError_t launch_fwd_win_bf16(int rows, int L, const FwdWinArgsT<__bf16>& a) {
+  static_assert(kWinLmin == 4 && kWinLmax == 20, "keep the PSF_CASE list in step with kWinLmin/kWinLmax");
+  static_assert(TGS >= 0 && TGS <= kWinTgsMaxBf16 && PSF_NT == 256, "not a compiled bf16 configuration");
+  if (rows == 2) return launch_L<__bf16, TGS, 2, 256>(L, a);
+  return hipErrorInvalidValue;
+}
+
+template hipError_t launch_fwd_win_bf16<PSF_TGS>(int rows, int L, const FwdWinArgsT<__bf16>& a);
+#else
 template <int TGS, int NT>
 hipError_t launch_fwd_win(int rows, int L, const FwdWinArgs& a) {
   static_assert(kWinLmin == 4 && kWinLmax == 20, "keep the PSF_CASE list in step with kWinLmin/kWinLmax");
   static_assert(win_pair_compiled(TGS, NT), "not a compiled (TGS, NT) pair");
-  if (rows == 2) return launch_L<TGS, 2, NT>(L, a);  // (the only compiled rows per thread: fwd_window_launch.h)
+  if (rows == 2) return launch_L<float, TGS, 2, NT>(L, a);  // (the only compiled rows per thread: fwd_window_launch.h)
   if constexpr (win_rows4_compiled(TGS, NT)) {
-    if (rows == 4) return launch_L<TGS, 4, NT>(L, a);
+    if (rows == 4) return launch_L<float, TGS, 4, NT>(L, a);
   }
   return hipErrorInvalidValue;
 }
 
 template hipError_t launch_fwd_win<PSF_TGS, PSF_NT>(int rows, int L, const FwdWinArgs& a);
+#endif
 
 }  // namespace psf

@@ -31,11 +31,12 @@ constexpr bool win_pair_compiled(int tgs, int nt) {
 // cfg4 (C=32) R=1 6.0 ~ R=2 6.1 < R=4 6.4; dV R=2 31.3 vs R=1 32.7; dW R=1 22.9 vs R=2 28.7. The other instances were
 // reachable through tuning knobs only ("fwd_rows", "bwd_rows") and went with them in round 5.
 
-struct FwdWinArgs {
-  const float* W;
-  const float* V;
-  const float* res;  // nullptr: no residual (selects the RES = false kernels)
-  float* out;
+template <typename T>
+struct FwdWinArgsT {
+  const T* W;
+  const T* V;
+  const T* res;  // nullptr: no residual (selects the RES = false kernels)
+  T* out;
   Geom gm;
   Offsets offs;
   int64_t w_total;  // B*N*L
@@ -44,9 +45,17 @@ struct FwdWinArgs {
   hipStream_t stream;
 };
 
+using FwdWinArgs = FwdWinArgsT<float>;
+
 // Launch the instance (L, TGS, R = rows, NT). Returns hipErrorInvalidValue when that instance is not compiled.
 template <int TGS, int NT>
 hipError_t launch_fwd_win(int rows, int L, const FwdWinArgs& a);
+
+// bf16 instances (fwd_window_inst.hip built with -DPSF_BF16): what the bf16 planner picks and nothing else — NT 256, R 2,
+// TGS 0..kWinTgsMaxBf16 (rows of up to 128 channels per chunk; wider rows are split into 128-channel chunks).
+constexpr int kWinTgsMaxBf16 = 4;
+template <int TGS>
+hipError_t launch_fwd_win_bf16(int rows, int L, const FwdWinArgsT<__bf16>& a);
 
 // window geometry for a (TGS, rows, NT) triple — mirrors FwdWinCfg
 inline int win_tile_rows(int tgs, int rows, int nt) { return (nt >> tgs) * rows; }

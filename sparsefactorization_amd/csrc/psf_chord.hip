@@ -475,9 +475,10 @@ bool pick_dv(const Tuning& tn, const void* W, int64_t B, int64_t N, int32_t L, i
 // Issue the one to two launches of a window kernel: full tiles on the predicate-free instance, the ragged last
 // tile of every sequence (if any) on the EDGE instance; everything on the EDGE instance when `all_edge`.
 // `launch` reads *gm and *edge, which are filled in before each call.
+// `vec`: elements per 16-byte channel group (4 for f32, 8 for bf16).
 template <typename F>
 int window_launches(const Tuning& tn, const WinPick& pk, bool all_edge, int64_t B, int64_t N, int32_t L, int64_t C,
-                    int64_t v_bstride, bool split_channels, Geom* gm, bool* edge, F launch, const char* what) {
+                    int64_t v_bstride, bool split_channels, Geom* gm, bool* edge, F launch, const char* what, int vec = 4) {
   const int tiles_all = pk.tiles_full + (pk.ragged ? 1 : 0);
   struct Part {
     int tile0, tiles;
@@ -492,7 +493,7 @@ int window_launches(const Tuning& tn, const WinPick& pk, bool all_edge, int64_t 
     if (pk.ragged) parts[np++] = {pk.tiles_full, 1, true};
   }
   for (int i = 0; i < np; ++i) {
-    if (int rc = make_geom(tn, B, N, L, C, 4, pk.tgs, pk.TR, split_channels, v_bstride, parts[i].tile0, parts[i].tiles, gm))
+    if (int rc = make_geom(tn, B, N, L, C, vec, pk.tgs, pk.TR, split_channels, v_bstride, parts[i].tile0, parts[i].tiles, gm))
       return rc;
     gm->aligned = pk.aligned && !parts[i].edge;
     *edge = parts[i].edge;
@@ -530,6 +531,93 @@ int fwd_window_f32(const Tuning& tn, const WinPick& pk, const float* W, const fl
                          [&] { return launch_win(pk, L, a); }, "chord_fwd_win launch");
 }
 
+// The bf16 window kernels' configuration (fwd_window_launch.h: kWinTgsMaxBf16): 16-byte groups of 8 channels, TGS 0..4 on
+// 256 threads x `rows` (forward and dV: 2, rows wider than 128 channels split into 128-channel chunks; dW: 1); no wide-row,
+// four-row or 512-thread configuration. Same near-offset and alignment rules as pick_window with 8 elements per 16-byte chunk
+// and 2-byte elements. `W` is the flat [B,N,L] array the kernel copies in 16-byte chunks (W, or dW for the dW kernel).
+bool pick_window_bf16(const Tuning& tn, const void* W, int64_t B, int64_t N, int32_t L, int64_t C, const Offsets& offs, bool vec_ok,
+                      WinPick* pick, int rows = 2) {
+  if (!vec_ok || L < kWinLmin || L > kWinLmax) return false;
+  const int64_t CG = C / 8;
+  const int tgs = ceil_log2(CG) > kWinTgsMaxBf16 ? kWinTgsMaxBf16 : ceil_log2(CG);
+  const int nt = 256;
+  const int TR = win_tile_rows(tgs, rows, nt);
+  if (N < 2 * (int64_t)TR) return false;  // the window may wrap at most once
+  int KN = 2;                             // offsets 0, 1, 2, ..., 2^(KN-2) <= TR
+  for (int t = TR; t > 1; t >>= 1) ++KN;
+  if (KN > L) KN = L;
+  for (int k = 0; k < KN; ++k)
+    if (offs.v[k] != chord_off(k)) return false;
+  pick->tgs = tgs;
+  pick->rows = rows;
+  pick->nt = nt;
+  pick->TR = TR;
+  pick->KN = KN;
+  pick->tiles_full = (int)(N / TR);
+  pick->ragged = (N % TR) != 0;
+  pick->aligned = (N % TR) == 0 && N * C * 2 < ((int64_t)1 << 31);
+  for (int k = KN; k < L; ++k)
+    if (offs.v[k] % TR != 0) pick->aligned = false;
+  const int TG = 1 << tgs;
+  pick->all_edge = (CG % TG) != 0 || !aligned_to(W, 16) || ((B * N * (int64_t)L) % 8) != 0 || !tn.fwd_split ||
+                   ragged_in_one_launch(tn, pick->ragged, B, N, L, C);
+  return true;
+}
+
+hipError_t launch_win_bf16(const WinPick& pk, int L, const FwdWinArgsT<__bf16>& a) {
+  switch (pk.tgs) {
+    case 0: return launch_fwd_win_bf16<0>(pk.rows, L, a);
+    case 1: return launch_fwd_win_bf16<1>(pk.rows, L, a);
+    case 2: return launch_fwd_win_bf16<2>(pk.rows, L, a);
+    case 3: return launch_fwd_win_bf16<3>(pk.rows, L, a);
+    case 4: return launch_fwd_win_bf16<4>(pk.rows, L, a);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_dw_bf16(const WinPick& pk, int L, const BwdWinArgsT<__bf16>& a) {
+  switch (pk.tgs) {
+    case 0: return launch_dw_win_bf16<0>(L, a);
+    case 1: return launch_dw_win_bf16<1>(L, a);
+    case 2: return launch_dw_win_bf16<2>(L, a);
+    case 3: return launch_dw_win_bf16<3>(L, a);
+    case 4: return launch_dw_win_bf16<4>(L, a);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_dv_bf16(const WinPick& pk, int L, const BwdWinArgsT<__bf16>& a) {
+  switch (pk.tgs) {
+    case 0: return launch_dv_win_bf16<0>(L, a);
+    case 1: return launch_dv_win_bf16<1>(L, a);
+    case 2: return launch_dv_win_bf16<2>(L, a);
+    case 3: return launch_dv_win_bf16<3>(L, a);
+    case 4: return launch_dv_win_bf16<4>(L, a);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// bf16 forward step on the window kernel. Workgroups per CU: fwd_window_f32's thresholds, keyed on TGS and tile count, are
+// f32 measurements applied to bf16 unchanged — a bf16 channel group holds twice the channels and a bf16 tile twice the rows of
+// the f32 configuration with the same TGS, so they describe other workloads here; not re-tuned for bf16.
+int fwd_window_bf16(const Tuning& tn, const WinPick& pk, const __bf16* W, const __bf16* V, const __bf16* res, __bf16* out, int64_t B,
+                    int64_t N, int32_t L, int64_t C, int64_t v_batch_stride, const Offsets& offs, hipStream_t s) {
+  FwdWinArgsT<__bf16> a;
+  a.W = W;
+  a.V = V;
+  a.res = res;
+  a.out = out;
+  a.offs = offs;
+  a.w_total = B * N * (int64_t)L;
+  a.stream = s;
+  const int knob = tn.fwd_wg_limit;
+  const int64_t tiles_total = B * (int64_t)(pk.tiles_full + (pk.ragged ? 1 : 0));
+  const bool three = (pk.tgs <= 1 && tiles_total >= 1536) || (pk.tgs == 2 && tiles_total >= 2048) || (pk.tgs == 3 && tiles_total >= 8192);
+  a.wg_per_cu = knob == 0 ? (three ? 3 : 0) : (knob == 1 ? 0 : knob);
+  return window_launches(tn, pk, pk.all_edge, B, N, L, C, v_batch_stride, true, &a.gm, &a.edge,
+                         [&] { return launch_win_bf16(pk, L, a); }, "chord_fwd_win<bf16> launch", 8);
+}
+
 template <typename T>
 int fwd_impl(const Tuning& tn, const T* W, const T* V, const T* res, T* out, int64_t B, int64_t N, int32_t L, int64_t C,
              int64_t v_batch_stride, const int64_t* offsets, void* stream) {
@@ -549,10 +637,14 @@ int fwd_impl(const Tuning& tn, const T* W, const T* V, const T* res, T* out, int
       (C % VECW == 0) && aligned_to(V, 16) && aligned_to(out, 16) && (!res || aligned_to(res, 16));
 
   const int variant = tn.fwd_variant;
-  if constexpr (sizeof(T) == 4) {  // the window kernels are compiled for f32 only (f64 exists for gradcheck)
+  if constexpr (sizeof(T) == 4) {  // window kernels: f32 and bf16 (f64 exists for gradcheck)
     WinPick pk;
     if (variant != 1 && pick_window(tn, W, B, N, L, C, offs, vec_ok, &pk, 2, true, 0, true))
       return fwd_window_f32(tn, pk, W, V, res, out, B, N, L, C, v_batch_stride, offs, s);
+  } else if constexpr (__is_same(T, __bf16)) {
+    WinPick pk;
+    if (variant != 1 && pick_window_bf16(tn, W, B, N, L, C, offs, vec_ok, &pk))
+      return fwd_window_bf16(tn, pk, W, V, res, out, B, N, L, C, v_batch_stride, offs, s);
   }
   if (variant == 2)
     return fail(PSF_E_TUNING, "fwd_variant=2 forced but the window kernel does not apply to N=%lld L=%d C=%lld",
@@ -586,7 +678,30 @@ int bwd_impl(const Tuning& tn, const T* dZ, const T* W, const T* V, T* dW, T* dV
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   constexpr int VECW = 16 / (int)sizeof(T);
 
-  if constexpr (sizeof(T) == 4) {  // LDS-window kernels (f32). Whatever they handle is cleared below.
+  if constexpr (__is_same(T, __bf16)) {  // bf16 LDS-window dW / dV (no fused step, no chunk-looping dW in bf16)
+    if (tn.bwd_variant != 1) {
+      const int64_t w_total = B * N * (int64_t)L;
+      WinPick pk;
+      if (dW && C / 8 <= (1 << kWinTgsMaxBf16) &&
+          pick_window_bf16(tn, dW, B, N, L, C, offs, (C % 8 == 0) && aligned_to(dZ, 16) && aligned_to(V, 16), &pk, 1)) {
+        // the dW tile store is chunk-clean only if every sequence starts on a 16-byte boundary
+        const bool all_edge = pk.all_edge || ((N * (int64_t)L) % 8) != 0;
+        BwdWinArgsT<__bf16> a{dZ, V, dW, Geom{}, offs, w_total, false, s};
+        int rc = window_launches(tn, pk, all_edge, B, N, L, C, v_batch_stride, false, &a.gm, &a.edge,
+                                 [&] { return launch_dw_bf16(pk, L, a); }, "chord_dw_win<bf16>", 8);
+        if (rc) return rc;
+        dW = nullptr;
+      }
+      if (dV && pick_window_bf16(tn, W, B, N, L, C, offs, (C % 8 == 0) && aligned_to(dZ, 16) && aligned_to(dV, 16), &pk, 2)) {
+        BwdWinArgsT<__bf16> a{dZ, W, dV, Geom{}, offs, w_total, false, s};
+        int rc = window_launches(tn, pk, pk.all_edge, B, N, L, C, N * C, true, &a.gm, &a.edge,
+                                 [&] { return launch_dv_bf16(pk, L, a); }, "chord_dv_win<bf16>", 8);
+        if (rc) return rc;
+        dV = nullptr;
+      }
+    }
+  }
+  if constexpr (sizeof(T) == 4) {  // LDS-window kernels (f32; f64 takes the generic kernels). Whatever they handle is cleared below.
     if (tn.bwd_variant != 1) {
       const int64_t w_total = B * N * (int64_t)L;
       const int TGmax = 1 << kWinTgsMax;
@@ -881,7 +996,8 @@ const char* psf_build_info(void) {
          " tall-skinny weight gradients (f32 MFMA), token embedding + positional add"
          ", wide producer MLPs (E <= 1024: stacked first layers as split-bf16 GEMMs from bf16 term planes, LDS-DMA ring)"
          " | mixer: W_m computed inside the chain step (per-step kernels; one LDS-resident launch for short sequences)"
-         " | arithmetic of the chord path: uncontracted mul+add, links ascending"
+         " | bf16 chord path: f32 accumulation, one rounding per element; fwd: generic + LDS-window<bf16, TG<=16, NT=256, R=2>; bwd: LDS-window dV<R=2> / dW<R=1><bf16, TG<=16> + generic"
+         " | arithmetic of the chord path: uncontracted mul+add (bf16: exact products fused), links ascending"
 #ifdef PSF_CSRC_HASH
          " | csrc=" PSF_CSRC_HASH  // build.csrc_hash() of the sources this library was built from (_lib.load compares)
 #endif
@@ -961,6 +1077,27 @@ int psf_chord_chain_fwd_f64(const double* const* W_steps, const double* V0, doub
                             int32_t use_residual, int64_t B, int64_t N, int32_t L, int64_t C,
                             int64_t v0_batch_stride, const int64_t* offsets, void* stream) {
   return chain_impl<double>(snapshot(), W_steps, V0, out_steps, M, use_residual, B, N, L, C, v0_batch_stride, offsets, stream);
+}
+
+int psf_chord_spmm_fwd_bf16(const uint16_t* W, const uint16_t* V, const uint16_t* res, uint16_t* out, int64_t B, int64_t N,
+                            int32_t L, int64_t C, int64_t v_batch_stride, const int64_t* offsets, void* stream) {
+  return fwd_impl<__bf16>(snapshot(), reinterpret_cast<const __bf16*>(W), reinterpret_cast<const __bf16*>(V),
+                          reinterpret_cast<const __bf16*>(res), reinterpret_cast<__bf16*>(out), B, N, L, C, v_batch_stride, offsets,
+                          stream);
+}
+
+int psf_chord_spmm_bwd_bf16(const uint16_t* dZ, const uint16_t* W, const uint16_t* V, uint16_t* dW, uint16_t* dV, int64_t B,
+                            int64_t N, int32_t L, int64_t C, int64_t v_batch_stride, const int64_t* offsets, void* stream) {
+  return bwd_impl<__bf16>(snapshot(), reinterpret_cast<const __bf16*>(dZ), reinterpret_cast<const __bf16*>(W),
+                          reinterpret_cast<const __bf16*>(V), reinterpret_cast<__bf16*>(dW), reinterpret_cast<__bf16*>(dV), B, N, L,
+                          C, v_batch_stride, offsets, stream);
+}
+
+int psf_chord_chain_fwd_bf16(const uint16_t* const* W_steps, const uint16_t* V0, uint16_t* const* out_steps, int32_t M,
+                             int32_t use_residual, int64_t B, int64_t N, int32_t L, int64_t C, int64_t v0_batch_stride,
+                             const int64_t* offsets, void* stream) {
+  return chain_impl<__bf16>(snapshot(), reinterpret_cast<const __bf16* const*>(W_steps), reinterpret_cast<const __bf16*>(V0),
+                            reinterpret_cast<__bf16* const*>(out_steps), M, use_residual, B, N, L, C, v0_batch_stride, offsets, stream);
 }
 
 int psf_chord_chain_bwd_supported(int64_t N, int32_t L, int64_t C, int32_t M) {
@@ -1194,7 +1331,7 @@ int psf_get_tuning(const char* key) {
 int psf_describe_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_bytes, char* buf, int32_t cap) {
   if (!buf || cap < 1) return fail(PSF_E_NULL, "buf is NULL");
   if (int rc = check_dims(B, N, L, C, N * C)) return rc;
-  if (elem_bytes != 4 && elem_bytes != 8) return fail(PSF_E_SHAPE, "elem_bytes must be 4 or 8");
+  if (elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return fail(PSF_E_SHAPE, "elem_bytes must be 2 (bf16), 4 or 8");
   Offsets offs;
   make_offsets(N, L, nullptr, &offs);
   const int vecw = 16 / elem_bytes;
@@ -1202,12 +1339,16 @@ int psf_describe_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_by
   WinPick pk;
   const Tuning tn = snapshot();
   const int variant = tn.fwd_variant;
-  if (variant != 1 && elem_bytes == 4 && pick_window(tn, nullptr, B, N, L, C, offs, vec_ok, &pk, 2, true, 0, true)) {
+  if (variant != 1 && elem_bytes == 2 && pick_window_bf16(tn, nullptr, B, N, L, C, offs, vec_ok, &pk)) {
+    snprintf(buf, cap, "chord_fwd_win_k<bf16,L=%d,TG=%d,R=%d,NT=%d> TR=%d near=%d far=%d tiles=%s", (int)L,
+             1 << pk.tgs, pk.rows, pk.nt, pk.TR, pk.KN, (int)L - pk.KN,
+             pk.all_edge ? "edge" : (pk.ragged ? "full+ragged" : (pk.aligned ? "full, aligned (scalar block addresses)" : "full")));
+  } else if (variant != 1 && elem_bytes == 4 && pick_window(tn, nullptr, B, N, L, C, offs, vec_ok, &pk, 2, true, 0, true)) {
     snprintf(buf, cap, "chord_fwd_win_k<f32,L=%d,TG=%d,R=%d,NT=%d> TR=%d near=%d far=%d tiles=%s", (int)L,
              1 << pk.tgs, pk.rows, pk.nt, pk.TR, pk.KN, (int)L - pk.KN,
              pk.all_edge ? "edge" : (pk.ragged ? "full+ragged" : (pk.aligned ? "full, aligned (scalar block addresses)" : "full")));
   } else {
-    snprintf(buf, cap, "chord_fwd_generic_k<%s,VEC=%d>", elem_bytes == 4 ? "f32" : "f64", vec_ok ? vecw : 1);
+    snprintf(buf, cap, "chord_fwd_generic_k<%s,VEC=%d>", elem_bytes == 2 ? "bf16" : elem_bytes == 4 ? "f32" : "f64", vec_ok ? vecw : 1);
   }
   return PSF_OK;
 }

@@ -112,6 +112,40 @@ template <>
 struct __attribute__((aligned(16))) Vec<double, 2> {
   double e[2];
 };
+template <>
+struct __attribute__((aligned(16))) Vec<__bf16, 8> {
+  __bf16 e[8];
+};
+
+// ---- accumulator type: f32 and f64 accumulate in their own type, bf16 in f32 (rounded to bf16 once, at the store) ----
+template <typename T>
+struct AccOf {
+  using type = T;
+};
+template <>
+struct AccOf<__bf16> {
+  using type = float;
+};
+template <typename T>
+using Acc = typename AccOf<T>::type;
+
+// load-and-widen / narrow-and-store: identities for f32 and f64; bf16 -> f32 is exact, f32 -> bf16 is a plain cast
+// (round to nearest even, a NaN stays a NaN: v_cvt_pk_bf16_f32 — not the integer-rounding trick, which can turn a NaN
+// into a zero or an infinity)
+template <typename T, int VEC>
+__device__ __forceinline__ Vec<Acc<T>, VEC> widen(const Vec<T, VEC>& v) {
+  Vec<Acc<T>, VEC> a;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) a.e[i] = (Acc<T>)v.e[i];
+  return a;
+}
+template <typename T, int VEC>
+__device__ __forceinline__ Vec<T, VEC> narrow(const Vec<Acc<T>, VEC>& a) {
+  Vec<T, VEC> v;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) v.e[i] = (T)a.e[i];
+  return v;
+}
 
 template <typename T, int VEC>
 __device__ __forceinline__ Vec<T, VEC> ld(const T* p) {
@@ -173,10 +207,21 @@ __device__ __forceinline__ void stg(PSF_GLOBAL char* p, const Vec<T, VEC>& v) {
   *reinterpret_cast<PSF_GLOBAL Raw*>(p) = r;
 }
 
+// acc + a * b in the accumulator type. f32 / f64: a rounded product, then a rounded sum (uncontracted, like the CPU path).
+// bf16: the product of two bf16 values is exact in f32, so one fused multiply-add rounds exactly where mul_rn + add_rn
+// would — the one place the chord kernels contract.
+template <typename T>
+__device__ __forceinline__ Acc<T> madd_rn(Acc<T> acc, T a, T b) {
+  if constexpr (__is_same(T, __bf16))
+    return __builtin_fmaf((float)a, (float)b, acc);
+  else
+    return add_rn(acc, mul_rn(a, b));
+}
+
 template <typename T, int VEC>
-__device__ __forceinline__ void axpy_rn(Vec<T, VEC>& acc, T w, const Vec<T, VEC>& x) {
+__device__ __forceinline__ void axpy_rn(Vec<Acc<T>, VEC>& acc, T w, const Vec<T, VEC>& x) {
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) acc.e[i] = add_rn(acc.e[i], mul_rn(w, x.e[i]));
+  for (int i = 0; i < VEC; ++i) acc.e[i] = madd_rn<T>(acc.e[i], w, x.e[i]);
 }
 
 // The chord pattern's link offsets (get_chord_indices_assym, SyntheticExperiments/psf.py:7-32): 0, 1, 2, 4, ...
