@@ -144,9 +144,16 @@ int psf_chord_spmm_fwd_f64(const double* W, const double* V, const double* res, 
  *   Alignment     pointers 2-byte aligned; the 16-byte vector kernels need C % 8 == 0 and 16-byte aligned row operands,
  *                 anything else runs the generic one-element-per-lane kernel.
  *   Kernels       forward step and dV: LDS-window kernels (rows of up to 128 channels per chunk), dW: LDS-window
- *                 kernel (rows of up to 128 channels), the generic kernels otherwise; chain: the per-step launches (no
- *                 one-launch chain and no fused backward step in bf16).
- * Not covered: float16, mixed dtypes, the bf16 producer / mixer / flat-head entries and psf_chord_chain_bwd.
+ *                 kernel (rows of up to 128 channels), the generic kernels otherwise. Forward chain: ONE launch with the
+ *                 sequence's X slice resident in LDS as bf16 (chord_chain_lds_k<bf16> for N * cc <= 2112 with cc = 1 or 2
+ *                 groups of 8 channels per workgroup; chord_chain_rows_k<bf16> with 16 channels per workgroup for
+ *                 1057 <= N <= 2048 and with 8 for 2113 <= N <= 4160), bit-identical to the per-step launches, when
+ *                 2 <= M <= 64, 2 <= L <= 20 (L <= 18 where three rows per thread are needed: 2048 < N * cc <= 2112),
+ *                 C % 8 == 0, V0 and every out_steps[m] 16-byte aligned, every W_steps[m] 2-byte aligned for odd L and
+ *                 4-byte aligned for even L, and the measured gate (knobs "chain_fused", "chain_cc") takes it;
+ *                 otherwise M per-step launches. psf_describe_chain_fwd_dtype names the route.
+ * Not covered: float16, mixed dtypes, the bf16 producer / mixer / flat-head entries, psf_chord_chain_bwd (the backward
+ *                 chain runs per step; there is no fused backward step in bf16).
  */
 int psf_chord_spmm_fwd_bf16(const uint16_t* W, const uint16_t* V, const uint16_t* res, uint16_t* out,
                             int64_t B, int64_t N, int32_t L, int64_t C, int64_t v_batch_stride,
@@ -536,6 +543,11 @@ int psf_describe_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_by
                      char* buf, int32_t cap);
 /* The same for a whole f32 forward chain of M steps: names the single-launch LDS-resident kernel when the chain takes it. */
 int psf_describe_chain_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, char* buf, int32_t cap);
+/* The same with the element size: 4 gives psf_describe_chain_fwd's string, 2 the bf16 chain's (chord_chain_lds_k<bf16,...> /
+ * chord_chain_rows_k<bf16,...> when an inference chain of aligned operands takes the one launch, else what
+ * psf_describe_fwd(..., 2, ...) says for its steps); any other size is PSF_E_SHAPE. Added without a version change. */
+int psf_describe_chain_fwd_dtype(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, int32_t elem_bytes, char* buf,
+                                 int32_t cap);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,7 @@ SIGNATURES = {
     "psf_get_tuning": ([ctypes.c_char_p], ctypes.c_int),
     "psf_describe_fwd": ([c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
     "psf_describe_chain_fwd": ([c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
+    "psf_describe_chain_fwd_dtype": ([c_i64, c_i64, c_i32, c_i64, c_i32, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
 }
 
 
@@ -213,9 +214,9 @@ def describe_fwd(B: int, N: int, L: int, C: int, elem_bytes: int = 4) -> str:
     return buf.value.decode()
 
 
-def describe_chain_fwd(B: int, N: int, L: int, C: int, M: int) -> str:
+def describe_chain_fwd(B: int, N: int, L: int, C: int, M: int, elem_bytes: int = 4) -> str:
     buf = ctypes.create_string_buffer(256)
-    check(load().psf_describe_chain_fwd(B, N, L, C, M, buf, 256), "psf_describe_chain_fwd")
+    check(load().psf_describe_chain_fwd_dtype(B, N, L, C, M, elem_bytes, buf, 256), "psf_describe_chain_fwd_dtype")
     return buf.value.decode()
 
 

@@ -66,14 +66,17 @@ hipError_t launch_L(int L, bool res, const ChainLdsPlan& p, const ChainArgs& a, 
 
 }  // namespace
 
-bool plan_chain_lds(int64_t N, int64_t C, int32_t L, int32_t M, ChainLdsPlan* p, int cc_pref, int64_t B) {
-  if (L < kChainLdsLmin || L > kChainLdsLmax || M < 1 || M > kChainMaxSteps || C % 4 != 0 || N < 1) return false;
-  const int64_t CG = C / 4;
+bool plan_chain_lds(int64_t N, int64_t C, int32_t L, int32_t M, ChainLdsPlan* p, int cc_pref, int64_t B, int elem_bytes) {
+  if (elem_bytes != 4 && elem_bytes != 2) return false;
+  const int vecw = 16 / elem_bytes;  // channels per 16-byte group
+  const int big_min_wgs = elem_bytes == 2 ? kChainBigMinWgsBf16 : kChainBigMinWgs;
+  if (L < kChainLdsLmin || L > kChainLdsLmax || M < 1 || M > kChainMaxSteps || C % vecw != 0 || N < 1) return false;
+  const int64_t CG = C / vecw;
   int cc = CG >= 2 ? 2 : 1;
   if (cc_pref == 1) cc = 1;
   p->big = 0;
   if (cc == 2 && N * 2 > kChainLdsMaxSlots && N * 2 <= kChainBigSlots &&
-      (cc_pref == 2 || (cc_pref == 0 && B * ((CG + 1) / 2) >= kChainBigMinWgs))) {
+      (cc_pref == 2 || (cc_pref == 0 && B * ((CG + 1) / 2) >= big_min_wgs))) {
     p->cc = 2;
     p->rows = 2;  // a thread owns both channel groups of its two rows
     p->threads = (int)(((N + 1) / 2 + 63) / 64 * 64);
@@ -82,7 +85,7 @@ bool plan_chain_lds(int64_t N, int64_t C, int32_t L, int32_t M, ChainLdsPlan* p,
     p->big = 1;
     return true;
   }
-  if (N > kChainLdsMaxSlots && N <= kChainLongRows && (cc_pref == 2 || (cc_pref == 0 && B * CG >= kChainBigMinWgs))) {
+  if (N > kChainLdsMaxSlots && N <= kChainLongRows && (cc_pref == 2 || (cc_pref == 0 && B * CG >= big_min_wgs))) {
     p->cc = 1;
     p->rows = kChainLongRowsPerThread;
     p->threads = (int)(((N + p->rows - 1) / p->rows + 63) / 64 * 64);
@@ -95,7 +98,8 @@ bool plan_chain_lds(int64_t N, int64_t C, int32_t L, int32_t M, ChainLdsPlan* p,
   if (N * cc > kChainLdsMaxSlots) return false;
   const int64_t slots = N * cc;                 // (row, channel group) pairs a workgroup owns
   const int R = slots <= 256 ? 1 : (slots <= kChainLdsSlots2 ? 2 : 3);  // 2 rows per thread: <= 512 threads up to 1024 slots
-  if (R == 3 && L > 14) return false;           // 3 rows x 2 W rows of L floats: beyond L = 14 the 768-thread instance spills
+  // 3 rows x 2 W rows of L floats: beyond L = 14 the 768-thread f32 instance spills
+  if (R == 3 && L > (elem_bytes == 2 ? kChainLdsRows3LmaxBf16 : 14)) return false;
   int64_t threads = (slots + R - 1) / R;
   threads = (threads + 63) / 64 * 64;           // whole waves; threads / cc row slots cover ceil(N / R) rows
   if (threads > 1024) return false;

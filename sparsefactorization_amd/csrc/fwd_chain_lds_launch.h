@@ -23,9 +23,16 @@ constexpr int kChainBigBytes = 2 * kChainBigSlots * 16;
 constexpr int kChainLongBytes = 2 * kChainLongRows * 16;
 constexpr int kChainLongRowsPerThread = 5;
 constexpr int kChainBigMinWgs = 256;
+// bfloat16 (fwd_chain_lds_bf16.h): a 16-byte slot is one row x 8 channels, so every slot count, byte limit and N limit above
+// holds unchanged and a workgroup covers 8 * cc channels. Compiled link counts: the same 2..20.
+constexpr int kChainBigMinWgsBf16 = 256;
+// three rows per thread (768 threads, 168 VGPRs): the residual instances at L = 19 and 20 spill 4-11 registers (code-object
+// metadata of the cross-compiled unit), so those two link counts are declined there and not compiled. Every other bf16
+// instance is free of scratch: <= 126 VGPRs on the 1024-thread ones (f32 needs R = 3 to stop at L = 14).
+constexpr int kChainLdsRows3LmaxBf16 = 18;
 
 struct ChainLdsPlan {
-  int cc;       // channel groups (of 4 channels) per workgroup: 1 or 2
+  int cc;       // channel groups (of 16 bytes: 4 f32 or 8 bf16 channels) per workgroup: 1 or 2
   int rows;     // rows per thread: 1, 2 or 3
   int threads;  // workgroup size (multiple of 64, <= 1024)
   int chunks;   // workgroups per sequence
@@ -37,9 +44,16 @@ struct ChainLdsPlan {
 // cc_pref: 0 = automatic (2 channel groups per workgroup when the row count allows; beyond 1056 rows, and the one-group
 // instance beyond 2112 rows, when the launch keeps >= kChainBigMinWgs workgroups: B sequences), 1 = force one (and no
 // instance beyond 2112 rows), 2 = the large instances wherever they fit
-bool plan_chain_lds(int64_t N, int64_t C, int32_t L, int32_t M, ChainLdsPlan* plan, int cc_pref = 0, int64_t B = 0);
+// elem_bytes: 4 (f32) or 2 (bf16: C a multiple of 8, kChainBigMinWgsBf16, kChainLdsRows3LmaxBf16)
+bool plan_chain_lds(int64_t N, int64_t C, int32_t L, int32_t M, ChainLdsPlan* plan, int cc_pref = 0, int64_t B = 0,
+                    int elem_bytes = 4);
 
 hipError_t launch_chain_lds(const ChainLdsPlan& plan, int L, bool res, const ChainArgs& args, const Offsets& offs,
                             int B, hipStream_t stream);
+
+// the bf16 instances (fwd_chain_lds_bf16.h, a translation unit of their own); plan from plan_chain_lds(..., elem_bytes = 2)
+struct ChainArgsBf16;
+hipError_t launch_chain_lds_bf16(const ChainLdsPlan& plan, int L, bool res, const ChainArgsBf16& args, const Offsets& offs,
+                                 int B, hipStream_t stream);
 
 }  // namespace psf

@@ -12,6 +12,7 @@
 #include "bwd_kernels.h"
 #include "bwd_window_launch.h"
 #include "bwd_chain_lds.h"
+#include "fwd_chain_lds_bf16.h"
 #include "fwd_chain_lds_launch.h"
 #include "fwd_kernels.h"
 #include "fwd_mlp_step_launch.h"
@@ -812,6 +813,52 @@ int bwd_impl(const Tuning& tn, const T* dZ, const T* W, const T* V, T* dW, T* dV
   return PSF_OK;
 }
 
+// Bit m set: step m's result reaches memory. A buffer that a later step overwrites (inference ping-pong) need not be stored.
+template <typename T>
+uint64_t chain_store_mask(T* const* out_steps, int32_t M) {
+  uint64_t mask = 0;
+  for (int m = 0; m < M; ++m) {
+    bool later = false;
+    for (int q = m + 1; q < M; ++q) later = later || out_steps[q] == out_steps[m];
+    if (!later) mask |= (uint64_t)1 << m;
+  }
+  return mask;
+}
+
+// ChainArgs / ChainArgsBf16 of a one-launch chain; vecw = channels per 16-byte group
+template <typename Args, typename T>
+void fill_chain_args(Args* a, const T* const* W_steps, const T* V0, T* const* out_steps, int32_t M, uint64_t store_mask, int64_t N,
+                     int64_t C, int vecw, int64_t v0_batch_stride, const ChainLdsPlan& plan, const Tuning& tn) {
+  for (int m = 0; m < kChainMaxSteps; ++m) {
+    a->W[m] = m < M ? W_steps[m] : nullptr;
+    a->out[m] = m < M ? out_steps[m] : nullptr;
+  }
+  a->store_mask = store_mask;
+  a->V0 = V0;
+  a->v0_bstride = v0_batch_stride;
+  a->M = M;
+  a->N = (int32_t)N;
+  a->C = (int32_t)C;
+  a->CG = (int32_t)(C / vecw);
+  a->chunks = plan.chunks;
+  a->xcd_remap = tn.xcd_remap && plan.chunks > 1 ? 1 : 0;  // (one workgroup per sequence shares nothing with its neighbours)
+}
+
+// Where the automatic route (chain_fused = 1) runs a bf16 chain in one launch: bf16's own measurements, not the f32 gate
+// (profiles/bf16_chain_ab.log, us per step, per-step launches / one launch, last result kept | every step kept):
+//   ListOps 2000 x 128 (rows_k G = 2, 256 workgroups): 12.2 / 5.9 | 13.0 / 6.8;  2048 x 64 (lds_k CC = 1): 6.6 / 3.6 | 7.3 / 4.2;
+//   Pathfinder 1024 x 32: 4.9 / 3.2 | 6.4 / 3.6;  attention map 1024 x 1024, broadcast eye: 9.8 / 6.3 | 11.0 / 6.7;
+//   synthetic N = 128 / 1024 / 2048 x 8: 5.2 / 2.6, 5.1 / 2.2, 4.8 / 3.1 | 6.4 / 3.8, 6.3 / 3.6, 6.2 / 3.5.
+// So, unlike f32, keeping every step costs the one launch nothing against the per-step route (its stores are the per-step
+// kernels' stores), and it is taken for every instance up to the 1 048 576 elements per sequence measured, EXCEPT the
+// long-row instance (rows_k G = 1, 2113 <= N <= 4160): the text task 4097 x 32 has 4 channel groups, so 128 workgroups of
+// 832 threads at B = 32 — half the CUs idle: 9.3 / 9.0 | 10.0 / 9.6, inside the rounds' spread when the last result is kept;
+// B = 16: 6.0 / 8.9 | 6.4 / 9.5, a loss. No bf16 launch of that instance with >= 256 workgroups has been measured, so it
+// is never automatic (chain_fused = 2 with chain_cc = 2 runs it).
+bool chain_bf16_gate(const ChainLdsPlan& plan, int64_t N, int64_t C) {
+  return plan.big != 2 && N * C <= 1048576;
+}
+
 template <typename T>
 int chain_impl(Tuning tn, const T* const* W_steps, const T* V0, T* const* out_steps, int32_t M, int32_t use_residual,
                int64_t B, int64_t N, int32_t L, int64_t C, int64_t v0_batch_stride, const int64_t* offsets,
@@ -856,13 +903,8 @@ int chain_impl(Tuning tn, const T* const* W_steps, const T* V0, T* const* out_st
     // 13.0 / 7.2 us per step; 4096 x 32: 11.8 / 6.5; 3000 x 32: 9.6 / 5.4; with every step kept the per-step kernels stay
     // (13.5 / 14.5), and below 256 workgroups too (B = 16: 7.4 / 6.6 last kept but 8.3 / 11.3 kept; C = 8: 6.4 / 6.6).
     const int cf = tn.chain_fused;
-    int kept = 0;  // step results that reach memory
-    for (int m = 0; m < M; ++m) {
-      bool later = false;
-      for (int q = m + 1; q < M; ++q) later = later || out_steps[q] == out_steps[m];
-      kept += later ? 0 : 1;
-    }
-    const bool few_kept = kept <= 2;
+    const uint64_t store_mask = M <= kChainMaxSteps ? chain_store_mask(out_steps, M) : ~(uint64_t)0;
+    const bool few_kept = __builtin_popcountll(store_mask) <= 2;  // step results that reach memory
     bool ok = cf && M >= 2 && M <= kChainMaxSteps && B >= 1 && plan_chain_lds(N, C, L, M, &plan, tn.chain_cc, B) &&
               (cf == 2 || few_kept || N * C <= 65536 || (N <= 1024 && N * C <= 131072) || (plan.big == 1 && N * C <= 524288)) &&
               aligned_to(V0, 16) && B * (int64_t)plan.chunks <= 0x7fffffff;
@@ -870,30 +912,32 @@ int chain_impl(Tuning tn, const T* const* W_steps, const T* V0, T* const* out_st
     if (ok) {
       if (int rc = check_dims(B, N, L, C, v0_batch_stride)) return rc;
       ChainArgs a;
-      a.store_mask = 0;
-      for (int m = 0; m < M; ++m) {
-        a.W[m] = W_steps[m];
-        a.out[m] = out_steps[m];
-        bool later = false;  // a buffer that a later step overwrites (inference ping-pong) need not be stored
-        for (int q = m + 1; q < M; ++q) later = later || out_steps[q] == out_steps[m];
-        if (!later) a.store_mask |= (uint64_t)1 << m;
-      }
-      for (int m = M; m < kChainMaxSteps; ++m) {
-        a.W[m] = nullptr;
-        a.out[m] = nullptr;
-      }
-      a.V0 = V0;
-      a.v0_bstride = v0_batch_stride;
-      a.M = M;
-      a.N = (int32_t)N;
-      a.C = (int32_t)C;
-      a.CG = (int32_t)(C / 4);
-      a.chunks = plan.chunks;
-      a.xcd_remap = tn.xcd_remap && plan.chunks > 1 ? 1 : 0;  // (one workgroup per sequence shares nothing with its neighbours)
+      fill_chain_args(&a, W_steps, V0, out_steps, M, store_mask, N, C, 4, v0_batch_stride, plan, tn);
       Offsets offs;
       make_offsets(N, L, offsets, &offs);
       hipError_t e = launch_chain_lds(plan, L, use_residual != 0, a, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
       if (e != hipSuccess) return fail_hip(e, "chord_chain_lds launch");
+      return PSF_OK;
+    }
+  } else if constexpr (__is_same(T, __bf16)) {
+    // The same one launch in bf16 (fwd_chain_lds_bf16.h: 8 channels per 16-byte LDS slot, bit-identical to the per-step bf16
+    // kernels). Needs C % 8 == 0, V0 and every stored result 16-byte aligned, and W rows that ceil(L / 2) aligned dwords
+    // cover: any 2-byte-aligned W for odd L, a 4-byte-aligned one for even L. Anything else takes the per-step launches.
+    // The gate is bf16's own (chain_bf16_gate above).
+    ChainLdsPlan plan;
+    const int cf = tn.chain_fused;
+    const uint64_t store_mask = M <= kChainMaxSteps ? chain_store_mask(out_steps, M) : ~(uint64_t)0;
+    bool ok = cf && M >= 2 && M <= kChainMaxSteps && B >= 1 && plan_chain_lds(N, C, L, M, &plan, tn.chain_cc, B, 2) &&
+              (cf == 2 || chain_bf16_gate(plan, N, C)) && aligned_to(V0, 16) && B * (int64_t)plan.chunks <= 0x7fffffff;
+    for (int m = 0; ok && m < M; ++m) ok = aligned_to(W_steps[m], L % 2 ? 2 : 4) && aligned_to(out_steps[m], 16);
+    if (ok) {
+      if (int rc = check_dims(B, N, L, C, v0_batch_stride)) return rc;
+      ChainArgsBf16 a;
+      fill_chain_args(&a, W_steps, V0, out_steps, M, store_mask, N, C, 8, v0_batch_stride, plan, tn);
+      Offsets offs;
+      make_offsets(N, L, offsets, &offs);
+      hipError_t e = launch_chain_lds_bf16(plan, L, use_residual != 0, a, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
+      if (e != hipSuccess) return fail_hip(e, "chord_chain_lds<bf16> launch");
       return PSF_OK;
     }
   }
@@ -1354,22 +1398,30 @@ int psf_describe_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_by
 }
 
 int psf_describe_chain_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, char* buf, int32_t cap) {
+  return psf_describe_chain_fwd_dtype(B, N, L, C, M, 4, buf, cap);
+}
+
+int psf_describe_chain_fwd_dtype(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, int32_t elem_bytes, char* buf,
+                                 int32_t cap) {
   if (!buf || cap < 1) return fail(PSF_E_NULL, "buf is NULL");
   if (int rc = check_dims(B, N, L, C, N * C)) return rc;
+  if (elem_bytes != 2 && elem_bytes != 4) return fail(PSF_E_SHAPE, "elem_bytes must be 2 (bf16) or 4");
   ChainLdsPlan plan;
   const Tuning tn = snapshot();
   const int cf = tn.chain_fused;
-  // (as an inference chain is run: only the last result kept)
-  if (cf && M >= 2 && M <= kChainMaxSteps && B >= 1 && plan_chain_lds(N, C, L, M, &plan, tn.chain_cc, B)) {
+  const char* ty = elem_bytes == 2 ? "bf16" : "f32";
+  // (as an inference chain is run: only the last result kept; bf16 under its own gate, operands taken as aligned)
+  if (cf && M >= 2 && M <= kChainMaxSteps && B >= 1 && plan_chain_lds(N, C, L, M, &plan, tn.chain_cc, B, elem_bytes) &&
+      (elem_bytes == 4 || cf == 2 || chain_bf16_gate(plan, N, C))) {
     if (plan.big)
-      snprintf(buf, cap, "chord_chain_rows_k<f32,L=%d,G=%d,R=%d> one launch for all %d steps, %d threads x %d rows x %d channels, %d workgroup(s) per sequence",
-               (int)L, plan.cc, plan.rows, (int)M, plan.threads, plan.rows, 4 * plan.cc, plan.chunks);
+      snprintf(buf, cap, "chord_chain_rows_k<%s,L=%d,G=%d,R=%d> one launch for all %d steps, %d threads x %d rows x %d channels, %d workgroup(s) per sequence",
+               ty, (int)L, plan.cc, plan.rows, (int)M, plan.threads, plan.rows, 16 / elem_bytes * plan.cc, plan.chunks);
     else
-      snprintf(buf, cap, "chord_chain_lds_k<f32,L=%d,CC=%d,R=%d> one launch for all %d steps, %d threads, %d workgroup(s) per sequence",
-               (int)L, plan.cc, plan.rows, (int)M, plan.threads, plan.chunks);
+      snprintf(buf, cap, "chord_chain_lds_k<%s,L=%d,CC=%d,R=%d> one launch for all %d steps, %d threads, %d workgroup(s) per sequence",
+               ty, (int)L, plan.cc, plan.rows, (int)M, plan.threads, plan.chunks);
     return PSF_OK;
   }
-  return psf_describe_fwd(B, N, L, C, 4, buf, cap);
+  return psf_describe_fwd(B, N, L, C, elem_bytes, buf, cap);
 }
 
 }  // extern "C"
