@@ -144,7 +144,14 @@ int psf_chord_spmm_fwd_f64(const double* W, const double* V, const double* res, 
  *   Alignment     pointers 2-byte aligned; the 16-byte vector kernels need C % 8 == 0 and 16-byte aligned row operands,
  *                 anything else runs the generic one-element-per-lane kernel.
  *   Kernels       forward step and dV: LDS-window kernels (rows of up to 128 channels per chunk), dW: LDS-window
- *                 kernel (rows of up to 128 channels), the generic kernels otherwise. Forward chain: ONE launch with the
+ *                 kernel (rows of up to 128 channels), the generic kernels otherwise. A backward step that wants both
+ *                 gradients runs ONE fused kernel (chord_bwd_fused_k<bf16>: dV and dW from one staging of the dZ rows)
+ *                 for rows of 8, 16, 32, 64 or 128 channels when 4 <= L <= 20, N is a multiple of the tile (2048 / C rows)
+ *                 and at least two tiles, the offsets are the chord pattern's near links with every far offset a multiple
+ *                 of the tile, all five operands are 16-byte aligned, B*N*L % 8 == 0, a batch element's rows span less
+ *                 than 2^31 bytes and the measured gate (knob "bwd_fused": 0 never, 1 automatic, 2 wherever it applies)
+ *                 takes it; dV and dW are bit-identical to the two-kernel route. psf_describe_bwd names the route.
+ *                 Forward chain: ONE launch with the
  *                 sequence's X slice resident in LDS as bf16 (chord_chain_lds_k<bf16> for N * cc <= 2112 with cc = 1 or 2
  *                 groups of 8 channels per workgroup; chord_chain_rows_k<bf16> with 16 channels per workgroup for
  *                 1057 <= N <= 2048 and with 8 for 2113 <= N <= 4160), bit-identical to the per-step launches, when
@@ -152,8 +159,11 @@ int psf_chord_spmm_fwd_f64(const double* W, const double* V, const double* res, 
  *                 C % 8 == 0, V0 and every out_steps[m] 16-byte aligned, every W_steps[m] 2-byte aligned for odd L and
  *                 4-byte aligned for even L, and the measured gate (knobs "chain_fused", "chain_cc") takes it;
  *                 otherwise M per-step launches. psf_describe_chain_fwd_dtype names the route.
- * Not covered: float16, mixed dtypes, the bf16 producer / mixer / flat-head entries, psf_chord_chain_bwd (the backward
- *                 chain runs per step; there is no fused backward step in bf16).
+ *                 Backward chain: psf_chord_chain_bwd_bf16 issues the per-step launches and the one residual sum inside
+ *                 the library (below).
+ * Not covered: float16, mixed dtypes, the bf16 producer / mixer / flat-head entries, a one-launch bf16 backward chain, and
+ *                 an edge instance of the bf16 fused backward step (ragged N, other far offsets, W / dW off their 16-byte
+ *                 boundary: those steps run the dW and dV window kernels).
  */
 int psf_chord_spmm_fwd_bf16(const uint16_t* W, const uint16_t* V, const uint16_t* res, uint16_t* out,
                             int64_t B, int64_t N, int32_t L, int64_t C, int64_t v_batch_stride,
@@ -224,6 +234,18 @@ int psf_chord_chain_bwd_supported(int64_t N, int32_t L, int64_t C, int32_t M);
 int psf_chord_chain_bwd_f32(const float* dOut, const float* const* W_steps, const float* V0, const float* const* X_steps,
                             float* const* dW_steps, float* dV0, float* const* dX_steps, int32_t M, int32_t use_residual,
                             int64_t B, int64_t N, int32_t L, int64_t C, const int64_t* offsets, void* stream);
+/*
+ * The same for bf16 (raw bits), arguments and validation as above. There is no one-launch kernel behind it and
+ * psf_chord_chain_bwd_supported is not consulted: it always issues the M per-step launches of psf_chord_spmm_bwd_bf16 (the
+ * fused step where that applies), handing the gradient from dX_steps[m] to the next step, and one psf_sum_tensors_bf16 pass
+ * for the residual — ((g_M + g_{M-1}) + ... + g_1) + g_0 summed in f32 and rounded once. Every dW_m and dV0 is bit-identical
+ * to M calls of psf_chord_spmm_bwd_bf16 followed by that sum. PSF_E_UNSUPPORTED (the caller runs the steps itself): dX_steps
+ * NULL, a residual chain with M + 1 > 32 or B*N*C % 8 != 0, knob "chain_bwd_fused" = 0.
+ */
+int psf_chord_chain_bwd_bf16(const uint16_t* dOut, const uint16_t* const* W_steps, const uint16_t* V0,
+                             const uint16_t* const* X_steps, uint16_t* const* dW_steps, uint16_t* dV0,
+                             uint16_t* const* dX_steps, int32_t M, int32_t use_residual,
+                             int64_t B, int64_t N, int32_t L, int64_t C, const int64_t* offsets, void* stream);
 
 /*
  * (Rounds 2-4 also exported training variants that kept a link-major side copy of W's far columns for the dV kernel —
@@ -548,6 +570,11 @@ int psf_describe_chain_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M
  * psf_describe_fwd(..., 2, ...) says for its steps); any other size is PSF_E_SHAPE. Added without a version change. */
 int psf_describe_chain_fwd_dtype(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, int32_t elem_bytes, char* buf,
                                  int32_t cap);
+/* The backward twin of psf_describe_fwd: the kernel(s) a backward step that wants both dW and dV would run on 16-byte aligned
+ * operands with a full-batch V and the chord offsets, under the current knobs — "chord_bwd_fused_k<bf16,L=15,TG=1,NT=256>
+ * TR=256 near=10 far=5 fronts=2" for the fused step, "<dW kernel> + <dV kernel>" for the two-kernel routes (window, chunk or
+ * generic kernels). elem_bytes: 2 (bf16), 4 (f32) or 8 (f64). Added without a version change. */
+int psf_describe_bwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_bytes, char* buf, int32_t cap);
 
 #ifdef __cplusplus
 }

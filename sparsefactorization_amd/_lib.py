@@ -40,6 +40,8 @@ SIGNATURES = {
     "psf_chord_chain_bwd_supported": ([c_i64, c_i32, c_i64, c_i32], ctypes.c_int),
     "psf_chord_chain_bwd_f32": ([c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_i32, c_i32,
                                  c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
+    "psf_chord_chain_bwd_bf16": ([c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_i32, c_i32,
+                                  c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
     "psf_linear_wgrad_workspace": ([c_i64, c_i32, c_i32], c_i64),
     "psf_linear_wgrad_f32": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),
     "psf_linear_wgrad_strided_f32": ([c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),
@@ -84,6 +86,7 @@ SIGNATURES = {
     "psf_set_tuning": ([ctypes.c_char_p, c_i32], ctypes.c_int),
     "psf_get_tuning": ([ctypes.c_char_p], ctypes.c_int),
     "psf_describe_fwd": ([c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
+    "psf_describe_bwd": ([c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
     "psf_describe_chain_fwd": ([c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
     "psf_describe_chain_fwd_dtype": ([c_i64, c_i64, c_i32, c_i64, c_i32, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
 }
@@ -174,7 +177,7 @@ def stream_ptr(dev) -> int:
     return cuda.current_stream(dev).cuda_stream
 
 
-PSF_E_UNSUPPORTED = -7  # psf_chord_chain_bwd_f32: no one-launch kernel for the shape (the caller runs the steps)
+PSF_E_UNSUPPORTED = -7  # psf_chord_chain_bwd_f32 / _bf16: the library does not run this chain (the caller runs the steps)
 
 
 def check(rc: int, what: str) -> None:
@@ -211,6 +214,13 @@ def get_tuning(key: str) -> int:
 def describe_fwd(B: int, N: int, L: int, C: int, elem_bytes: int = 4) -> str:
     buf = ctypes.create_string_buffer(256)
     check(load().psf_describe_fwd(B, N, L, C, elem_bytes, buf, 256), "psf_describe_fwd")
+    return buf.value.decode()
+
+
+def describe_bwd(B: int, N: int, L: int, C: int, elem_bytes: int = 4) -> str:
+    """The kernel(s) of a backward step that wants both gradients (aligned operands, chord offsets, current knobs)."""
+    buf = ctypes.create_string_buffer(256)
+    check(load().psf_describe_bwd(B, N, L, C, elem_bytes, buf, 256), "psf_describe_bwd")
     return buf.value.decode()
 
 

@@ -26,9 +26,9 @@ ARCH = "gfx950"
 WIN_TGS = list(range(7))
 
 HEADERS = ["psf_common.h", "fwd_kernels.h", "fwd_window.h", "fwd_window_launch.h", "bwd_kernels.h",
-           "bwd_window.h", "bwd_dw_chunk.h", "bwd_window_launch.h", "fwd_chain_lds.h", "fwd_chain_lds_bf16.h", "fwd_chain_lds_launch.h", "bwd_chain_lds.h", "fwd_mlp_step.h", "fwd_mlp_step_launch.h", "mixer_lds.h", "mixer_lds_launch.h", "mlp_x3_image.h", "mlp_fwd_x3.h", "mlp_x3_common.h", "mlp_planes.h", "x3_gemm.h",
+           "bwd_window.h", "bwd_dw_chunk.h", "bwd_window_launch.h", "bwd_fused.h", "bwd_fused_bf16.h", "fwd_chain_lds.h", "fwd_chain_lds_bf16.h", "fwd_chain_lds_launch.h", "bwd_chain_lds.h", "fwd_mlp_step.h", "fwd_mlp_step_launch.h", "mixer_lds.h", "mixer_lds_launch.h", "mlp_x3_image.h", "mlp_fwd_x3.h", "mlp_x3_common.h", "mlp_planes.h", "x3_gemm.h",
            os.path.join("..", "..", "include", "psf_chord.h")]
-SOURCES = ["psf_chord.hip", "fwd_window_inst.hip", "bwd_window_inst.hip", "linear_wgrad.hip",
+SOURCES = ["psf_chord.hip", "fwd_window_inst.hip", "bwd_window_inst.hip", "bwd_fused_bf16_inst.hip", "linear_wgrad.hip",
            "fwd_chain_lds_inst.hip", "fwd_chain_lds_bf16_inst.hip", "bwd_chain_lds_inst.hip", "fwd_mlp_step_inst.hip", "mixer_lds_inst.hip", "embed.hip", "flat_head.hip", "sum_tensors.hip", "adam.hip", "mlp_fwd.hip", "mlp_fwd_x3.hip", "mlp_bwd.hip", "mlp_wide.hip", "stream_mix.hip"]
 
 # -ffp-contract=off: products and sums stay separate roundings (bitwise parity with the CPU oracle).
@@ -105,6 +105,9 @@ def _unit_table():
                           [f"-DPSF_TGS={t}", "-DPSF_BF16"]))
             units.append((os.path.join(OBJ_DIR, f"bwd_window_bf16_tgs{t}.o"), os.path.join(CSRC, "bwd_window_inst.hip"),
                           [f"-DPSF_TGS={t}", "-DPSF_BF16"]))
+            # the bf16 fused backward step (bwd_window_launch.h: kFusedBf16TgsMax), units of its own: the f32 units are untouched
+            units.append((os.path.join(OBJ_DIR, f"bwd_fused_bf16_tgs{t}.o"), os.path.join(CSRC, "bwd_fused_bf16_inst.hip"),
+                          [f"-DPSF_TGS={t}"]))
     # the forward step that computes its own W tile (fwd_mlp_step_launch.h: kMlpStepTgsMax)
     for t in range(4):
         units.append((os.path.join(OBJ_DIR, f"fwd_mlp_step_tgs{t}.o"), os.path.join(CSRC, "fwd_mlp_step_inst.hip"),
@@ -129,7 +132,7 @@ def _unit_weight(unit) -> int:
     """Rough compile cost of a unit (seconds on this container), for the order in which the pool starts them."""
     name = os.path.basename(unit[0])
     for prefix, w in (("fwd_mlp_step", 30), ("mlp_bwd", 28), ("fwd_chain_lds", 26), ("mlp_wide", 24), ("fwd_window", 16),
-                      ("bwd_window_mid", 14), ("bwd_window", 12), ("mixer_lds", 10), ("mlp_fwd", 8), ("psf_chord", 8)):
+                      ("bwd_window_mid", 14), ("bwd_window", 12), ("bwd_fused_bf16", 10), ("mixer_lds", 10), ("mlp_fwd", 8), ("psf_chord", 8)):
         if name.startswith(prefix):
             return w
     return 3

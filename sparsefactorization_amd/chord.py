@@ -312,13 +312,16 @@ class _ChordChain(torch.autograd.Function):
         dev = _require_hip(g, V0, *Ws)
         lib = _lib.load()
         off = _lib.offsets_array(ctx.offsets)
-        # the whole backward chain in ONE library call (psf_chord_chain_bwd_f32): one launch with the running gradient resident in
+        # the whole backward chain in ONE library call (psf_chord_chain_bwd_f32 / _bf16): f32 has one launch with the running gradient resident in
         # LDS for short sequences of narrow rows (the synthetic tasks up to N = 1024; csrc/bwd_chain_lds.h), the M per-step launches
         # and the one-pass residual sum issued by the library otherwise — same kernels, same order and same bits as the loop
         # below, without M trips through ctypes and 2 M allocations (the small LRA models are bound by the host)
-        if (g.dtype == torch.float32 and stride0 == N * C and all(need_w) and M >= 1
+        # bf16 (psf_chord_chain_bwd_bf16): no one-launch kernel — always the per-step launches and the one residual sum, issued by
+        # the library; PSF_E_UNSUPPORTED where psf_sum_tensors_bf16's limits do not hold, and the loop below runs instead
+        is_bf16 = g.dtype == torch.bfloat16
+        if ((g.dtype == torch.float32 or is_bf16) and stride0 == N * C and all(need_w) and M >= 1
                 and not any(t.data_ptr() % 16 for t in (g, V0, *steps))):  # (views at odd offsets: the loop's kernels take them)
-            one_launch = bool(lib.psf_chord_chain_bwd_supported(N, L, C, M))
+            one_launch = not is_bf16 and bool(lib.psf_chord_chain_bwd_supported(N, L, C, M))
             dWb = torch.empty((M, B, N, L), dtype=g.dtype, device=dev)
             dWs = list(dWb.unbind(0))
             dV0 = torch.empty((B, N, C), dtype=g.dtype, device=dev)
@@ -330,10 +333,11 @@ class _ChordChain(torch.autograd.Function):
                 dXb = torch.empty((M, B, N, C), dtype=g.dtype, device=dev)
                 dx_tab = (ctypes.c_void_p * M)(*[dXb[m].data_ptr() for m in range(M)])
             with torch.cuda.device(dev):
-                rc = lib.psf_chord_chain_bwd_f32(g.data_ptr(), w_tab, V0.data_ptr(), x_tab, dw_tab, dV0.data_ptr(), dx_tab, M,
-                                                 1 if ctx.use_residual else 0, B, N, L, C, off, _stream_ptr(dev))
+                chain_bwd = lib.psf_chord_chain_bwd_bf16 if is_bf16 else lib.psf_chord_chain_bwd_f32
+                rc = chain_bwd(g.data_ptr(), w_tab, V0.data_ptr(), x_tab, dw_tab, dV0.data_ptr(), dx_tab, M,
+                               1 if ctx.use_residual else 0, B, N, L, C, off, _stream_ptr(dev))
             if rc != _lib.PSF_E_UNSUPPORTED:
-                _lib.check(rc, "psf_chord_chain_bwd_f32")
+                _lib.check(rc, "psf_chord_chain_bwd")
                 return (dV0.reshape(ctx.v_shape) if need_v0 else None, None, None, *dWs)
             dWs = [None] * M
         fn = getattr(lib, "psf_chord_spmm_bwd" + _suffix(g))

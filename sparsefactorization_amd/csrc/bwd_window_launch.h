@@ -34,6 +34,11 @@ template <int TGS>
 hipError_t launch_dw_win_bf16(int L, const BwdWinArgsT<__bf16>& a);
 template <int TGS>
 hipError_t launch_dv_win_bf16(int L, const BwdWinArgsT<__bf16>& a);
+// bf16 fused dV + dW step (bwd_fused_bf16.h, units bwd_fused_bf16_inst.hip): 256 threads x 1 row (tile = 256 >> TGS rows), rows of
+// exactly 8 << TGS channels; arguments as the f32 fused step (WV = W, V2 = V, out = dV, out2 = dW)
+constexpr int kFusedBf16TgsMax = 4;
+template <int TGS>
+hipError_t launch_bwd_fused_bf16(int L, const BwdWinArgsT<__bf16>& a);
 // chunk-looping dW (bwd_dw_chunk.h) for rows of >= 32 channels: 8 or 16 lanes per row chunk (TGS 3 / 4), 256 threads,
 // one row per thread. r02 sweep (profiles/r02c_dw_sweep*.log, us per launch at ListOps N=2000 C=128 / genome C=32):
 // TG=8 R=1 21.0 (15.3 in one launch) / 20.6; TG=16 R=1 15.2 / 20.7; R=2 25.5 / 24.8; 1024 threads x 1 row 28.2 / 33.5;

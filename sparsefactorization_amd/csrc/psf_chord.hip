@@ -598,6 +598,69 @@ hipError_t launch_dv_bf16(const WinPick& pk, int L, const BwdWinArgsT<__bf16>& a
   }
 }
 
+hipError_t launch_fused_step_bf16(int tgs, int L, const BwdWinArgsT<__bf16>& a) {
+  switch (tgs) {
+    case 0: return launch_bwd_fused_bf16<0>(L, a);
+    case 1: return launch_bwd_fused_bf16<1>(L, a);
+    case 2: return launch_bwd_fused_bf16<2>(L, a);
+    case 3: return launch_bwd_fused_bf16<3>(L, a);
+    case 4: return launch_bwd_fused_bf16<4>(L, a);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The automatic route (bwd_fused = 1) of the bf16 fused step: only the widths and lengths where it measured faster than the two
+// window kernels by more than the run-to-run spread (profiles/bf16_bwd_fused_ab.md). Until a shape has been measured it stays on
+// the two kernels; bwd_fused = 2 takes the fused step wherever it applies.
+bool fused_step_auto_bf16(int64_t B, int64_t N, int64_t C) {
+  (void)B, (void)N, (void)C;
+  return false;
+}
+// Fronts and workgroups per CU: f32's rules (two fronts from N = 8192 on; no limit) kept unmeasured for bf16 unless the .md says otherwise
+int fused_fronts_auto_bf16(int64_t N) { return N >= 8192 ? 2 : 1; }
+int fused_wg_auto_bf16(int64_t tiles_total, int tgs) {
+  (void)tiles_total, (void)tgs;
+  return 0;
+}
+
+// The bf16 fused dV + dW step (bwd_fused_bf16.h): full tiles of rows of exactly 8 << tgs channels (8..128), N a multiple of the
+// tile (256 >> tgs rows) and at least two tiles, chord near offsets, every far offset a multiple of the tile, all five operands
+// 16-byte aligned and W / dW chunk-clean, a batch element's rows below 2^31 bytes. Knob bwd_fused: 0 never, 1 where the fused
+// step measured faster than the two window kernels (fused_step_auto_bf16), 2 wherever it applies. There is no bf16 edge
+// instance: ragged N, other far offsets and misaligned W / dW stay on the two window kernels.
+bool pick_fused_step_bf16(const Tuning& tn, const void* dZ, const void* W, const void* V, const void* dW, const void* dV, int64_t B,
+                          int64_t N, int32_t L, int64_t C, int64_t v_bstride, const Offsets& offs, WinPick* pk) {
+  const int knob = tn.bwd_fused;
+  if (!knob || L < kWinLmin || L > kWinLmax) return false;
+  if (C != 8 && C != 16 && C != 32 && C != 64 && C != 128) return false;
+  const int tgs = ceil_log2(C / 8);
+  const int nt = 256;
+  const int TR = nt >> tgs;
+  if (N % TR != 0 || N < 2 * (int64_t)TR) return false;
+  if (knob == 1 && !fused_step_auto_bf16(B, N, C)) return false;
+  if (!aligned_to(dZ, 16) || !aligned_to(W, 16) || !aligned_to(V, 16) || !aligned_to(dW, 16) || !aligned_to(dV, 16)) return false;
+  if ((B * N * (int64_t)L) % 8 != 0 || (v_bstride != 0 && v_bstride != N * C)) return false;
+  int KN = 2;
+  for (int t = TR; t > 1; t >>= 1) ++KN;
+  if (KN > L) KN = L;
+  for (int k = 0; k < KN; ++k)
+    if (offs.v[k] != chord_off(k)) return false;
+  for (int k = KN; k < L; ++k)
+    if (offs.v[k] % TR != 0) return false;  // far row blocks are TR-aligned (scalar block addresses in the kernel)
+  if (N * C * 2 >= ((int64_t)1 << 31)) return false;
+  pk->tgs = tgs, pk->rows = 1, pk->nt = nt, pk->TR = TR, pk->KN = KN;
+  pk->tiles_full = (int)(N / TR), pk->ragged = false, pk->all_edge = false;
+  return true;
+}
+
+// Interleaved fronts of the bf16 fused step (Geom::ileave): the shift, 0 = one front
+int fused_fronts_shift_bf16(const Tuning& tn, int64_t N, int tiles_full) {
+  const int fronts = tn.bwd_fronts ? tn.bwd_fronts : fused_fronts_auto_bf16(N);
+  int sh = 0;
+  while ((2 << sh) <= fronts) ++sh;
+  return sh > 0 && tiles_full % (1 << sh) == 0 ? sh : 0;
+}
+
 // bf16 forward step on the window kernel. Workgroups per CU: fwd_window_f32's thresholds, keyed on TGS and tile count, are
 // f32 measurements applied to bf16 unchanged — a bf16 channel group holds twice the channels and a bf16 tile twice the rows of
 // the f32 configuration with the same TGS, so they describe other workloads here; not re-tuned for bf16.
@@ -679,10 +742,22 @@ int bwd_impl(const Tuning& tn, const T* dZ, const T* W, const T* V, T* dW, T* dV
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   constexpr int VECW = 16 / (int)sizeof(T);
 
-  if constexpr (__is_same(T, __bf16)) {  // bf16 LDS-window dW / dV (no fused step, no chunk-looping dW in bf16)
+  if constexpr (__is_same(T, __bf16)) {  // bf16: the fused step, else LDS-window dW / dV (no chunk-looping dW in bf16)
     if (tn.bwd_variant != 1) {
       const int64_t w_total = B * N * (int64_t)L;
       WinPick pk;
+      if (dW && dV && pick_fused_step_bf16(tn, dZ, W, V, dW, dV, B, N, L, C, v_batch_stride, offs, &pk)) {
+        BwdWinArgsT<__bf16> a{dZ, W, dV, Geom{}, offs, w_total, false, s};
+        a.V2 = V;
+        a.out2 = dW;
+        a.wg_per_cu = tn.bwd_fused_wg_limit ? tn.bwd_fused_wg_limit : fused_wg_auto_bf16(B * (int64_t)pk.tiles_full, pk.tgs);
+        if (int rc = make_geom(tn, B, N, L, C, 8, pk.tgs, pk.TR, false, v_batch_stride, 0, pk.tiles_full, &a.gm)) return rc;
+        a.gm.ileave = fused_fronts_shift_bf16(tn, N, pk.tiles_full);
+        hipError_t e = launch_fused_step_bf16(pk.tgs, L, a);
+        if (e != hipSuccess) return fail_hip(e, "chord_bwd_fused<bf16>");
+        dW = nullptr;
+        dV = nullptr;
+      }
       if (dW && C / 8 <= (1 << kWinTgsMaxBf16) &&
           pick_window_bf16(tn, dW, B, N, L, C, offs, (C % 8 == 0) && aligned_to(dZ, 16) && aligned_to(V, 16), &pk, 1)) {
         // the dW tile store is chunk-clean only if every sequence starts on a 16-byte boundary
@@ -1040,7 +1115,8 @@ const char* psf_build_info(void) {
          " tall-skinny weight gradients (f32 MFMA), token embedding + positional add"
          ", wide producer MLPs (E <= 1024: stacked first layers as split-bf16 GEMMs from bf16 term planes, LDS-DMA ring)"
          " | mixer: W_m computed inside the chain step (per-step kernels; one LDS-resident launch for short sequences)"
-         " | bf16 chord path: f32 accumulation, one rounding per element; fwd: generic + LDS-window<bf16, TG<=16, NT=256, R=2>; bwd: LDS-window dV<R=2> / dW<R=1><bf16, TG<=16> + generic"
+         " | bf16 chord path: f32 accumulation, one rounding per element; fwd: generic + LDS-window<bf16, TG<=16, NT=256, R=2>; bwd: fused dV+dW step<bf16, TG<=16, NT=256> (aligned full tiles), LDS-window dV<R=2> / dW<R=1><bf16, TG<=16> + generic;"
+         " backward chain issued by the library (per-step launches)"
          " | arithmetic of the chord path: uncontracted mul+add (bf16: exact products fused), links ascending"
 #ifdef PSF_CSRC_HASH
          " | csrc=" PSF_CSRC_HASH  // build.csrc_hash() of the sources this library was built from (_lib.load compares)
@@ -1199,6 +1275,46 @@ int psf_chord_chain_bwd_f32(const float* dOut, const float* const* W_steps, cons
   if (use_residual) {
     terms[nterms++] = g;  // ((g_M + g_{M-1}) + ... + g_1) + g_0
     return psf_sum_tensors_f32(terms, nterms, B * N * C, dV0, stream);
+  }
+  return PSF_OK;
+}
+
+// The bf16 backward chain in one library call: always the M per-step launches of psf_chord_spmm_bwd_bf16 (the fused step where
+// it applies), the gradient handed from dX_steps[m] to the next step, and one psf_sum_tensors_bf16 pass for the residual —
+// ((g_M + g_{M-1}) + ... + g_1) + g_0 in f32, rounded once: what chord.py's loop does, without M trips through the caller's FFI.
+// There is no one-launch bf16 backward kernel behind it.
+int psf_chord_chain_bwd_bf16(const uint16_t* dOut, const uint16_t* const* W_steps, const uint16_t* V0, const uint16_t* const* X_steps,
+                             uint16_t* const* dW_steps, uint16_t* dV0, uint16_t* const* dX_steps, int32_t M, int32_t use_residual,
+                             int64_t B, int64_t N, int32_t L, int64_t C, const int64_t* offsets, void* stream) {
+  if (M < 1) return fail(PSF_E_SHAPE, "M must be >= 1");
+  if (!dOut || !W_steps || !V0 || !X_steps || !dW_steps || !dV0) return fail(PSF_E_NULL, "a required pointer is NULL");
+  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
+  if (!g_chain_bwd_fused.load()) return PSF_E_UNSUPPORTED;  // (knob off: the caller runs the steps itself)
+  // the per-step path needs the M gradient buffers and, with the residual, psf_sum_tensors_bf16's limits
+  if (!dX_steps || (use_residual && (M + 1 > 32 || (B * N * C) % 8 != 0))) return PSF_E_UNSUPPORTED;
+  if (B == 0) return PSF_OK;
+  for (int m = 0; m < M; ++m) {
+    const uint16_t* x = m == 0 ? V0 : X_steps[m];
+    if (!W_steps[m] || !x || !dW_steps[m]) return fail(PSF_E_NULL, "step %d: NULL pointer", m);
+    if (dW_steps[m] == W_steps[m]) return fail(PSF_E_ALIAS, "step %d: dW aliases W", m);
+    if (!dX_steps[m]) return fail(PSF_E_NULL, "step %d: dX_steps[m] is NULL", m);
+  }
+  const Tuning tn = snapshot();
+  const uint16_t* g = dOut;
+  const uint16_t* terms[33];
+  int nterms = 0;
+  for (int m = M - 1; m >= 0; --m) {
+    if (use_residual) terms[nterms++] = g;
+    uint16_t* dx = (m == 0 && !use_residual) ? dV0 : dX_steps[m];
+    if (int rc = bwd_impl<__bf16>(tn, reinterpret_cast<const __bf16*>(g), reinterpret_cast<const __bf16*>(W_steps[m]),
+                                  reinterpret_cast<const __bf16*>(m == 0 ? V0 : X_steps[m]), reinterpret_cast<__bf16*>(dW_steps[m]),
+                                  reinterpret_cast<__bf16*>(dx), B, N, L, C, N * C, offsets, stream))
+      return rc;
+    g = dx;
+  }
+  if (use_residual) {
+    terms[nterms++] = g;
+    return psf_sum_tensors_bf16(terms, nterms, B * N * C, dV0, stream);
   }
   return PSF_OK;
 }
@@ -1394,6 +1510,59 @@ int psf_describe_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_by
   } else {
     snprintf(buf, cap, "chord_fwd_generic_k<%s,VEC=%d>", elem_bytes == 2 ? "bf16" : elem_bytes == 4 ? "f32" : "f64", vec_ok ? vecw : 1);
   }
+  return PSF_OK;
+}
+
+// The kernel(s) of one backward step that wants both gradients, operands taken as 16-byte aligned, a full-batch V: the picks
+// of bwd_impl in bwd_impl's order.
+int psf_describe_bwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_bytes, char* buf, int32_t cap) {
+  if (!buf || cap < 1) return fail(PSF_E_NULL, "buf is NULL");
+  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
+  if (elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return fail(PSF_E_SHAPE, "elem_bytes must be 2 (bf16), 4 or 8");
+  Offsets offs;
+  make_offsets(N, L, nullptr, &offs);
+  const int vecw = 16 / elem_bytes;
+  const bool vec_ok = C % vecw == 0;
+  const char* ty = elem_bytes == 2 ? "bf16" : elem_bytes == 4 ? "f32" : "f64";
+  const Tuning tn = snapshot();
+  const bool win = tn.bwd_variant != 1 && B >= 1;
+  WinPick pk;
+  if (win && elem_bytes == 2 && pick_fused_step_bf16(tn, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, L, C, N * C, offs, &pk)) {
+    snprintf(buf, cap, "chord_bwd_fused_k<bf16,L=%d,TG=%d,NT=%d> TR=%d near=%d far=%d fronts=%d", (int)L, 1 << pk.tgs, pk.nt, pk.TR,
+             pk.KN, (int)L - pk.KN, 1 << fused_fronts_shift_bf16(tn, N, pk.tiles_full));
+    return PSF_OK;
+  }
+  if (win && elem_bytes == 4 && pick_fused_step(tn, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, L, C, N * C, offs, &pk)) {
+    const int fronts = tn.bwd_fronts ? tn.bwd_fronts : (N >= 8192 ? 2 : 1);
+    int sh = 0;
+    while ((2 << sh) <= fronts) ++sh;
+    if (!(sh > 0 && pk.tiles_full % (1 << sh) == 0)) sh = 0;
+    snprintf(buf, cap, "chord_bwd_fused_k<f32,L=%d,TG=%d,NT=%d> TR=%d near=%d far=%d fronts=%d", (int)L, 1 << pk.tgs, pk.nt, pk.TR,
+             pk.KN, (int)L - pk.KN, 1 << sh);
+    return PSF_OK;
+  }
+  if (win && elem_bytes == 4 && pick_fused_edge_step(tn, nullptr, nullptr, nullptr, N, L, C, N * C, offs, &pk)) {
+    snprintf(buf, cap, "chord_bwd_fused_edge_k<f32,L=%d,TG=%d,NT=%d> TR=%d near=%d far=%d", (int)L, 1 << pk.tgs, pk.nt, pk.TR, pk.KN,
+             (int)L - pk.KN);
+    return PSF_OK;
+  }
+  char dw[112], dv[112];
+  snprintf(dw, sizeof(dw), "chord_dw_generic_k<%s,VEC=%d>", ty, vec_ok ? vecw : 1);
+  snprintf(dv, sizeof(dv), "chord_dv_generic_k<%s,VEC=%d>", ty, vec_ok ? vecw : 1);
+  if (win && elem_bytes == 2) {
+    if (C / 8 <= (1 << kWinTgsMaxBf16) && pick_window_bf16(tn, nullptr, B, N, L, C, offs, vec_ok, &pk, 1))
+      snprintf(dw, sizeof(dw), "chord_dw_win_k<bf16,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
+    if (pick_window_bf16(tn, nullptr, B, N, L, C, offs, vec_ok, &pk, 2))
+      snprintf(dv, sizeof(dv), "chord_dv_win_k<bf16,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
+  } else if (win && elem_bytes == 4) {
+    if (tn.dw_variant != 1 && pick_dw_chunk(tn, nullptr, B, N, L, C, offs, vec_ok, &pk))
+      snprintf(dw, sizeof(dw), "chord_dw_chunk_k<f32,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
+    else if (C / 4 <= (1 << kWinTgsMax) && pick_window(tn, nullptr, B, N, L, C, offs, vec_ok, &pk, 1, false))
+      snprintf(dw, sizeof(dw), "chord_dw_win_k<f32,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
+    if (pick_dv(tn, nullptr, B, N, L, C, offs, vec_ok, &pk))
+      snprintf(dv, sizeof(dv), "chord_dv_win_k<f32,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
+  }
+  snprintf(buf, cap, "%s + %s", dw, dv);
   return PSF_OK;
 }
 
