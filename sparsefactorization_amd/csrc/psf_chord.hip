@@ -3,11 +3,16 @@
 // Host side of the drop-in boundary that replaces torch_sparse.spmm at SyntheticExperiments/psf.py:178-184
 // (and its copies) and spmul_cuda.{forward_host,backward_host} (spmul/spmul_cuda.cu:31-59,114-159).
 // Stateless apart from a thread-local error string and a few process-wide tuning integers.
+//
+// Every step is planned once (plan_fwd / plan_bwd / plan_chain fill a plain struct) and the plan is either executed
+// (fwd_impl / bwd_impl / chain_impl, from the caller's pointers) or printed (psf_describe_*, operands taken as aligned:
+// nullptr, which aligned_to accepts). The order of the picks, the gates and the thresholds exist in the planners only.
 
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "bwd_kernels.h"
 #include "bwd_window_launch.h"
@@ -42,44 +47,54 @@ int fail_hip(hipError_t e, const char* what) {
   return (int)e;
 }
 
-std::atomic<int> g_fwd_variant{0};  // 0 auto, 1 generic, 2 window
-std::atomic<int> g_bwd_variant{0};  // 0 auto, 1 generic
-std::atomic<int> g_xcd_remap{1};
-// 1 = full tiles on the predicate-free kernel + the ragged last tiles in a second small launch, except on small
-// problems (one predicated launch); 2 = always two launches; 0 = always one predicated launch
-std::atomic<int> g_fwd_split{1};
-// dV workgroup: 0 = auto (512 threads x 1 row for rows of <= 8 channels), 1 = 256 threads x 2 rows
-std::atomic<int> g_dv_threads{0};
-std::atomic<int> g_bwd_fused{1};  // 0 = never, 1 = auto, 2 = wherever the fused step kernel applies
-std::atomic<int> g_dw_variant{0};   // dW: 0 = auto (chunk-looping kernel for C >= 32), 1 = whole-row window kernel, 2 = chunk forced
-std::atomic<int> g_dw_tgs{0};       // chunk-looping dW: 0 = auto, 4 = 8 lanes per row chunk, 5 = 16 lanes
-std::atomic<int> g_chain_fused{1};  // 1 = short sequences run the whole chain in one LDS-resident launch
-std::atomic<int> g_chain_bwd_fused{1};  // psf_chord_chain_bwd_f32: 1 = the one-launch kernel where it fits, 0 = never (PSF_E_UNSUPPORTED)
-std::atomic<int> g_chain_cc{0};     // fused chain: 0 = auto channel groups per workgroup, 1 = one, 2 = two wherever it fits
-// Rows of >= 64 channels: 0 = one workgroup spans the whole row (default); 1 = 32-channel chunks on 1024-thread
-// workgroups (256-row tiles, far links 6 -> 2 at L=12); 2 = 32-channel chunks on 256-thread workgroups.
-// r01 sweep (us/launch): cfg3 C=128: 18.9 / 23.2 / 21.8; attention map C=1024: 19.2 / 20.5 / 20.9; C=64: 10.2 / 9.4 /
-// 10.0 — contiguous whole-row bursts beat fewer far links, so 0 stays the default.
-std::atomic<int> g_fwd_wide{0};
-// Forward window kernel, workgroups per CU: 0 = auto (3 for narrow rows on large launches), 1 = no limit, 2..4 = cap
-std::atomic<int> g_fwd_wg_limit{0};
-std::atomic<int> g_bwd_fused_wg_limit{0};  // fused backward step: 0 = whatever fits (five of 256 threads at C = 8), n = at most n
-// Per-step launches of a chain: 1 = alternate the direction in which each XCD walks its tile range
-std::atomic<int> g_chain_zigzag{1};
-std::atomic<int> g_bwd_fronts{0};     // fused backward step: interleaved fronts per batch element, 0 = auto (2 from N = 8192 on), 1, 2, 4, 8
-std::atomic<int> g_fwd_rows{0};       // forward window kernel, rows per thread: 0 = auto, 2, 4 (4: where compiled, fwd_window_launch.h)
-std::atomic<int> g_bwd_ablate{0};      // fused backward step, -DPSF_BWD_ABLATE_LAB builds only (bwd_fused.h: ABL); ignored otherwise
-std::atomic<int> g_mixer_ablate{0};    // timing experiments on that kernel: bit 0 no MLP arithmetic, 1 no multiply-add chain, 2 no far rows, 3 no data rows
-std::atomic<int> g_mixer_lds{1};       // psf_mixer_fwd_*: 1 = short sequences take the single-launch LDS-resident mixer (mixer_lds.h)
-std::atomic<int> g_mixer_wg_limit{0};  // step kernel that computes its own W (fwd_mlp_step.h): 0 = whatever fits, n = at most n per CU
+// Every knob of this unit, once: X(name, lo, hi, default). The list makes the atomic g_<name>, the member of Tuning, its
+// load in snapshot() and the row of g_knobs that psf_set_tuning / psf_get_tuning search by name.
+//   fwd_variant: 0 auto, 1 generic, 2 window
+//   bwd_variant: 0 auto, 1 generic
+//   fwd_split: 1 = full tiles on the predicate-free kernel + the ragged last tiles in a second small launch, except on small
+//     problems (one predicated launch); 2 = always two launches; 0 = always one predicated launch
+//   dv_threads: dV workgroup: 0 = auto (512 threads x 1 row for rows of <= 8 channels), 1 = 256 threads x 2 rows
+//   bwd_fused: 0 = never, 1 = auto, 2 = wherever the fused step kernel applies
+//   dw_variant: dW: 0 = auto (chunk-looping kernel for C >= 32), 1 = whole-row window kernel, 2 = chunk forced
+//   dw_tgs: chunk-looping dW: 0 = auto, 4 = 8 lanes per row chunk, 5 = 16 lanes
+//   chain_fused: 1 = short sequences run the whole chain in one LDS-resident launch
+//   chain_bwd_fused: psf_chord_chain_bwd_f32: 1 = the one-launch kernel where it fits, 0 = never (PSF_E_UNSUPPORTED)
+//   chain_cc: fused chain: 0 = auto channel groups per workgroup, 1 = one, 2 = two wherever it fits
+//   fwd_wide: Rows of >= 64 channels: 0 = one workgroup spans the whole row (default); 1 = 32-channel chunks on 1024-thread
+//     workgroups (256-row tiles, far links 6 -> 2 at L=12); 2 = 32-channel chunks on 256-thread workgroups.
+//     r01 sweep (us/launch): cfg3 C=128: 18.9 / 23.2 / 21.8; attention map C=1024: 19.2 / 20.5 / 20.9; C=64: 10.2 / 9.4 /
+//     10.0 — contiguous whole-row bursts beat fewer far links, so 0 stays the default.
+//   fwd_wg_limit: Forward window kernel, workgroups per CU: 0 = auto (3 for narrow rows on large launches), 1 = no limit,
+//     2..4 = cap
+//   bwd_fused_wg_limit: fused backward step: 0 = whatever fits (five of 256 threads at C = 8), n = at most n
+//   chain_zigzag: Per-step launches of a chain: 1 = alternate the direction in which each XCD walks its tile range
+//   bwd_fronts: fused backward step: interleaved fronts per batch element, 0 = auto (2 from N = 8192 on), 1, 2, 4, 8
+//   fwd_rows: forward window kernel, rows per thread: 0 = auto, 2, 4 (4: where compiled, fwd_window_launch.h)
+//   bwd_ablate: fused backward step, -DPSF_BWD_ABLATE_LAB builds only (bwd_fused.h: ABL); ignored otherwise
+//   mixer_ablate: timing experiments on that kernel: bit 0 no MLP arithmetic, 1 no multiply-add chain, 2 no far rows, 3 no
+//     data rows
+//   mixer_lds: psf_mixer_fwd_*: 1 = short sequences take the single-launch LDS-resident mixer (mixer_lds.h)
+//   mixer_wg_limit: step kernel that computes its own W (fwd_mlp_step.h): 0 = whatever fits, n = at most n per CU
+#define PSF_KNOBS(X)                                                                                                    \
+  X(fwd_variant, 0, 2, 0) X(bwd_variant, 0, 1, 0) X(xcd_remap, 0, 1, 1) X(fwd_split, 0, 2, 1) X(fwd_wide, 0, 4, 0)      \
+  X(dw_variant, 0, 2, 0) X(dv_threads, 0, 1, 0) X(bwd_fused, 0, 2, 1) X(bwd_fused_wg_limit, 0, 5, 0) X(dw_tgs, 0, 5, 0) \
+  X(fwd_wg_limit, 0, 4, 0) X(chain_zigzag, 0, 1, 1) X(mixer_wg_limit, 0, 4, 0) X(mixer_lds, 0, 1, 1)                    \
+  X(mixer_ablate, 0, 15, 0) X(bwd_ablate, 0, 1023, 0) X(bwd_fronts, 0, 8, 0) X(fwd_rows, 0, 4, 0)                       \
+  X(chain_fused, 0, 2, 1) X(chain_cc, 0, 2, 0) X(chain_bwd_fused, 0, 1, 1)
+// The knobs that other units read (mlp_fwd.hip, mlp_wide.hip declare them extern): X(key, variable, lo, hi, default).
+//   mlp_variant: Fused producer MLPs: 0 = auto (split-bf16 kernel of mlp_fwd_x3.hip where it applies, else the f32-MFMA kernel
+//     of mlp_fwd.hip with all images LDS-resident when they fit), 1 = f32 MFMA streaming, 2 = f32 MFMA resident, 3 = split-bf16
+//   wide_fuse: wide producer MLPs: second layers of narrow-output MLPs in the forward GEMM's epilogue
+#define PSF_EXTERN_KNOBS(X) X(mlp_variant, psf_g_mlp_variant, 0, 3, 0) X(wide_fuse, psf_g_wide_fuse, 0, 1, 1)
+
+#define X(name, lo, hi, def) std::atomic<int> g_##name{def};
+PSF_KNOBS(X)
+#undef X
 
 }  // namespace
-// Fused producer MLPs: 0 = auto (split-bf16 kernel of mlp_fwd_x3.hip where it applies, else the f32-MFMA kernel of
-// mlp_fwd.hip with all images LDS-resident when they fit), 1 = f32 MFMA streaming, 2 = f32 MFMA resident, 3 = split-bf16
-std::atomic<int> psf_g_mlp_variant{0};
-// Fused producer MLP backward: 0 = auto (= 3), 1 = all-f32-MFMA kernel, 2 = split-bf16 kernel with steps 4 and 5 left on
-// the f32 instruction, 3 = split-bf16 kernel on dual-use LDS planes (all five GEMMs on the bf16 matrix pipe)
-std::atomic<int> psf_g_wide_fuse{1};  // wide producer MLPs: second layers of narrow-output MLPs in the forward GEMM's epilogue
+#define X(key, var, lo, hi, def) std::atomic<int> var{def};
+PSF_EXTERN_KNOBS(X)
+#undef X
 namespace {
 
 struct Knob {
@@ -88,52 +103,44 @@ struct Knob {
   int lo, hi;
 };
 Knob g_knobs[] = {
-    {"fwd_variant", &g_fwd_variant, 0, 2}, {"bwd_variant", &g_bwd_variant, 0, 1}, {"xcd_remap", &g_xcd_remap, 0, 1},
-    {"fwd_split", &g_fwd_split, 0, 2},
-    {"fwd_wide", &g_fwd_wide, 0, 4},
-    {"dw_variant", &g_dw_variant, 0, 2},
-    {"dv_threads", &g_dv_threads, 0, 1},
-    {"bwd_fused", &g_bwd_fused, 0, 2},
-    {"bwd_fused_wg_limit", &g_bwd_fused_wg_limit, 0, 5},
-    {"dw_tgs", &g_dw_tgs, 0, 5},
-    {"fwd_wg_limit", &g_fwd_wg_limit, 0, 4},
-    {"chain_zigzag", &g_chain_zigzag, 0, 1},
-    {"mixer_wg_limit", &g_mixer_wg_limit, 0, 4},
-    {"mixer_lds", &g_mixer_lds, 0, 1},
-    {"mixer_ablate", &g_mixer_ablate, 0, 15},
-    {"bwd_ablate", &g_bwd_ablate, 0, 1023},
-    {"bwd_fronts", &g_bwd_fronts, 0, 8},
-    {"fwd_rows", &g_fwd_rows, 0, 4},
-    {"chain_fused", &g_chain_fused, 0, 2},
-    {"chain_cc", &g_chain_cc, 0, 2},
-    {"chain_bwd_fused", &g_chain_bwd_fused, 0, 1},
-    {"mlp_variant", &psf_g_mlp_variant, 0, 3},
-    {"wide_fuse", &psf_g_wide_fuse, 0, 1},
+#define X(name, lo, hi, def) {#name, &g_##name, lo, hi},
+    PSF_KNOBS(X)
+#undef X
+#define X(key, var, lo, hi, def) {#key, &var, lo, hi},
+    PSF_EXTERN_KNOBS(X)
+#undef X
 };
 
 // One consistent view of the knobs per entry-point call: every extern "C" function takes ONE snapshot and hands it down, so
 // a psf_set_tuning from another thread changes the next call, never the middle of one; `walk_backwards` (zigzag of a chain's
 // odd steps) travels in it too instead of in thread-local state.
 struct Tuning {
-  int fwd_variant, bwd_variant, xcd_remap, fwd_split, dv_threads, bwd_fused, dw_variant,
-      dw_tgs, chain_fused, chain_cc, fwd_wide, fwd_wg_limit, bwd_fused_wg_limit, chain_zigzag, mixer_wg_limit, mixer_ablate, mixer_lds, bwd_ablate, bwd_fronts, fwd_rows;
+#define X(name, lo, hi, def) int name;
+  PSF_KNOBS(X)
+#undef X
   bool walk_backwards;
 };
 
 Tuning snapshot() {
   Tuning t;
-  t.fwd_variant = g_fwd_variant.load(), t.bwd_variant = g_bwd_variant.load(), t.xcd_remap = g_xcd_remap.load();
-  t.fwd_split = g_fwd_split.load();
-  t.dv_threads = g_dv_threads.load(), t.bwd_fused = g_bwd_fused.load();
-  t.dw_variant = g_dw_variant.load(), t.dw_tgs = g_dw_tgs.load(), t.chain_fused = g_chain_fused.load();
-  t.chain_cc = g_chain_cc.load(), t.fwd_wide = g_fwd_wide.load(), t.fwd_wg_limit = g_fwd_wg_limit.load();
-  t.bwd_fused_wg_limit = g_bwd_fused_wg_limit.load(), t.chain_zigzag = g_chain_zigzag.load();
-  t.mixer_wg_limit = g_mixer_wg_limit.load(), t.mixer_ablate = g_mixer_ablate.load(), t.mixer_lds = g_mixer_lds.load();
-  t.bwd_ablate = g_bwd_ablate.load();
-  t.bwd_fronts = g_bwd_fronts.load();
-  t.fwd_rows = g_fwd_rows.load();
+#define X(name, lo, hi, def) t.name = g_##name.load();
+  PSF_KNOBS(X)
+#undef X
   t.walk_backwards = false;
   return t;
+}
+
+// The run-time channel-group shift `tgs` as a template argument: f(std::integral_constant<int, TGS>) for LO <= tgs <= HI,
+// hipErrorInvalidValue outside. The ranges at the call sites name compiled instances only (a launcher that no unit
+// compiles would fail the link).
+template <int LO, int HI, typename F>
+hipError_t with_tgs(int tgs, F&& f) {
+  if constexpr (LO > HI) {
+    return hipErrorInvalidValue;
+  } else {
+    if (tgs == LO) return f(std::integral_constant<int, LO>{});
+    return with_tgs<LO + 1, HI>(tgs, f);
+  }
 }
 
 int ceil_log2(int64_t x) {
@@ -216,8 +223,25 @@ int generic_geom(const Tuning& tn, int64_t B, int64_t N, int32_t L, int64_t C, i
 }
 
 // ------------------------------------------------------------------------------------------------------
-// window-kernel selection
+// element types, window-kernel selection
 // ------------------------------------------------------------------------------------------------------
+// What the planners need to know of an element type. f32 has every configuration; the bf16 window kernels
+// (fwd_window_launch.h: kWinTgsMaxBf16) take 16-byte groups of 8 channels, TGS 0..4 on 256 threads x `rows` (forward and dV: 2,
+// rows wider than 128 channels split into 128-channel chunks; dW: 1); f64 exists for gradcheck, on the generic kernels.
+struct Elem {
+  const char* name;
+  int bytes, vec;   // element bytes; elements per 16-byte group
+  bool window;      // LDS-window kernels, the fused backward step and the one-launch chain exist
+  int tgs_max;      // widest window-kernel channel-group shift
+  bool f32_routes;  // the wide-row, four-row and 512-thread window configurations, the chunk-looping dW and the EDGE
+                    // instance of the fused step exist
+};
+constexpr Elem kBf16{"bf16", 2, 8, true, kWinTgsMaxBf16, false}, kF32{"f32", 4, 4, true, kWinTgsMax, true},
+    kF64{"f64", 8, 2, false, 0, false};
+const Elem& elem_of(int bytes) { return bytes == 2 ? kBf16 : bytes == 4 ? kF32 : kF64; }
+template <typename T>
+constexpr bool kIsBf16 = std::is_same<T, __bf16>::value;
+
 struct WinPick {
   int tgs, rows, nt, TR, KN;
   int tiles_full;  // row tiles per sequence with all TR rows < N
@@ -226,58 +250,52 @@ struct WinPick {
   bool aligned = false;  // Geom::aligned
 };
 
-#define PSF_TGS_SWITCH(FN, ARGS)                 \
-  switch (pk.tgs) {                              \
-    case 0: return FN<0, 256> ARGS;              \
-    case 1: return FN<1, 256> ARGS;              \
-    case 2: return FN<2, 256> ARGS;              \
-    case 3: return FN<3, 256> ARGS;              \
-    case 4: return FN<4, 256> ARGS;              \
-    case 5: return FN<5, 256> ARGS;              \
-    case 6: return FN<6, 256> ARGS;              \
-    default: return hipErrorInvalidValue;        \
-  }
+void set_pick(WinPick* pk, int tgs, int rows, int nt, int TR, int KN, int64_t N) {
+  pk->tgs = tgs, pk->rows = rows, pk->nt = nt, pk->TR = TR, pk->KN = KN;
+  pk->tiles_full = (int)(N / TR), pk->ragged = (N % TR) != 0;
+}
 
+// The near links of a tile of TR rows: offsets 0, 1, 2, ..., 2^(KN-2) <= TR, at most L of them. They are compile-time
+// constants in the window kernels, so 0 (no kernel) unless the caller's first KN offsets are the chord pattern's.
+int near_links(int TR, int32_t L, const Offsets& offs) {
+  int KN = 2;
+  for (int t = TR; t > 1; t >>= 1) ++KN;
+  if (KN > L) KN = L;
+  for (int k = 0; k < KN; ++k)
+    if (offs.v[k] != chord_off(k)) return 0;
+  return KN;
+}
+
+// Run-time configuration -> compiled instance, by argument type.
 hipError_t launch_win(const WinPick& pk, int L, const FwdWinArgs& a) {
   if (pk.nt == kWideThreads) return pk.tgs == kWideTgs ? launch_fwd_win<kWideTgs, kWideThreads>(pk.rows, L, a) : hipErrorInvalidValue;
-  PSF_TGS_SWITCH(launch_fwd_win, (pk.rows, L, a))
+  return with_tgs<0, kWinTgsMax>(pk.tgs, [&](auto t) { return launch_fwd_win<t(), 256>(pk.rows, L, a); });
 }
-
+hipError_t launch_win(const WinPick& pk, int L, const FwdWinArgsT<__bf16>& a) {
+  return with_tgs<0, kWinTgsMaxBf16>(pk.tgs, [&](auto t) { return launch_fwd_win_bf16<t()>(pk.rows, L, a); });
+}
 hipError_t launch_dv(const WinPick& pk, int L, const BwdWinArgs& a) {
   if (pk.nt == kWideThreads) return pk.tgs == kWideTgs ? launch_dv_win<kWideTgs, kWideThreads>(pk.rows, L, a) : hipErrorInvalidValue;
-  if (pk.nt == kDvMidThreads) {
-    switch (pk.tgs) {
-      case 0: return launch_dv_win<0, kDvMidThreads>(pk.rows, L, a);
-      case 1: return launch_dv_win<1, kDvMidThreads>(pk.rows, L, a);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  PSF_TGS_SWITCH(launch_dv_win, (pk.rows, L, a))
+  if (pk.nt == kDvMidThreads)
+    return with_tgs<0, kDvMidTgsMax>(pk.tgs, [&](auto t) { return launch_dv_win<t(), kDvMidThreads>(pk.rows, L, a); });
+  return with_tgs<0, kWinTgsMax>(pk.tgs, [&](auto t) { return launch_dv_win<t(), 256>(pk.rows, L, a); });
 }
-#undef PSF_TGS_SWITCH
-
-hipError_t launch_fused_step(int tgs, int L, const BwdWinArgs& a) {
-  switch (tgs) {
-    case 0: return launch_bwd_fused<0>(L, a);
-    case 1: return launch_bwd_fused<1>(L, a);
-    case 2: return launch_bwd_fused<2>(L, a);
-    case 3: return launch_bwd_fused<3>(L, a);
-    case 4: return launch_bwd_fused<4>(L, a);
-    case 5: return launch_bwd_fused<5>(L, a);
-    default: return hipErrorInvalidValue;
-  }
+hipError_t launch_dv(const WinPick& pk, int L, const BwdWinArgsT<__bf16>& a) {
+  return with_tgs<0, kWinTgsMaxBf16>(pk.tgs, [&](auto t) { return launch_dv_win_bf16<t()>(L, a); });
 }
-
-hipError_t launch_fused_edge_step(int tgs, int L, const BwdWinArgs& a) {
-  switch (tgs) {
-    case 0: return launch_bwd_fused_edge<0>(L, a);
-    case 1: return launch_bwd_fused_edge<1>(L, a);
-    case 2: return launch_bwd_fused_edge<2>(L, a);
-    case 3: return launch_bwd_fused_edge<3>(L, a);
-    case 4: return launch_bwd_fused_edge<4>(L, a);
-    case 5: return launch_bwd_fused_edge<5>(L, a);
-    default: return hipErrorInvalidValue;
-  }
+hipError_t launch_dw(bool chunk, const WinPick& pk, int L, const BwdWinArgs& a) {
+  if (chunk) return with_tgs<kDwChunkTgsMin, kDwChunkTgsMax>(pk.tgs, [&](auto t) { return launch_dw_chunk<t()>(L, a); });
+  return with_tgs<0, kWinTgsMax>(pk.tgs, [&](auto t) { return launch_dw_win<t()>(pk.rows, L, a); });
+}
+hipError_t launch_dw(bool, const WinPick& pk, int L, const BwdWinArgsT<__bf16>& a) {
+  return with_tgs<0, kWinTgsMaxBf16>(pk.tgs, [&](auto t) { return launch_dw_win_bf16<t()>(L, a); });
+}
+hipError_t launch_fused(bool edge, int tgs, int L, const BwdWinArgs& a) {
+  if (edge) return with_tgs<0, kFusedTgsMax>(tgs, [&](auto t) { return launch_bwd_fused_edge<t()>(L, a); });
+  return with_tgs<0, kFusedTgsMax>(tgs, [&](auto t) { return launch_bwd_fused<t()>(L, a); });
+}
+hipError_t launch_fused(bool, int tgs, int L, const BwdWinArgsT<__bf16>& a) {
+  return with_tgs<0, kFusedBf16TgsMax>(tgs, [&](auto t) { return launch_bwd_fused_bf16<t()>(L, a); });
 }
 
 // Row widths the fused backward step takes: exactly 4 << tgs channels with a whole row inside one workgroup. Rounds 3-5: up
@@ -285,55 +303,88 @@ hipError_t launch_fused_edge_step(int tgs, int L, const BwdWinArgs& a) {
 // 64 channels at every length — N = 1024: 11.3 / 8.9; 2000: 20.2 / 15.3; 2048: 21.6 / 17.4; 2049 (edge instance): 23.6 / 18.8;
 // 4096: 42.8 / 38.3; 4097: 23.8 / 18.7; 8192: 43.7 / 42.9; 16384: 49.3 / 47.2 — and 128 channels up to N = 4096 — ListOps'
 // N = 2000: 39.3 / 35.4; 2001: 40.1 / 36.9; 1024, 4096, 4097 equal — but not beyond (N = 16384: 96.3 / 102.8: tiles of 8 rows).
-bool fused_step_width(int64_t C, int64_t N) {
+// bf16 (bwd_fused_bf16.h): rows of exactly 8 << tgs channels (8..128).
+bool fused_step_width(const Elem& el, int64_t C, int64_t N) {
+  if (!el.f32_routes) return C == 8 || C == 16 || C == 32 || C == 64 || C == 128;
   return C == 4 || C == 8 || C == 16 || C == 32 || C == 64 || (C == 128 && N <= 4096);
+}
+
+// The automatic route (bwd_fused = 1). f32: wherever the step applies. bf16 (was fused_step_auto_bf16): only the widths and
+// lengths where it measured faster than the two window kernels by more than the run-to-run spread
+// (profiles/bf16_bwd_fused_ab.md). Until a shape has been measured it stays on the two kernels; bwd_fused = 2 takes the fused
+// step wherever it applies.
+bool fused_step_auto(const Elem& el, int64_t B, int64_t N, int64_t C) {
+  (void)B, (void)N, (void)C;
+  return el.f32_routes;
 }
 
 // The EDGE instance of the fused step (bwd_fused.h: chord_bwd_fused_edge_k) takes what pick_fused_step turns away for its
 // geometry: any N >= two tiles (N = 2^k + 1 with a CLS token), any far offsets, W / dW at any alignment. Same rows (fused_step_width), chord near offsets, 16-byte aligned row operands. Knob bwd_fused = 2 keeps its meaning (the aligned instance or
 // nothing); 1 (default) lets this one in.
-bool pick_fused_edge_step(const Tuning& tn, const void* dZ, const void* V, const void* dV, int64_t N, int32_t L, int64_t C,
-                          int64_t v_bstride, const Offsets& offs, WinPick* pk) {
-  if (tn.bwd_fused != 1 || L < kWinLmin || L > kWinLmax || !fused_step_width(C, N)) return false;
-  const int tgs = C == 4 ? 0 : C == 8 ? 1 : C == 16 ? 2 : C == 32 ? 3 : C == 64 ? 4 : 5;
-  const int nt = 256;
-  const int TR = nt >> tgs;
+// There is no bf16 edge instance: ragged N, other far offsets and misaligned W / dW stay on the two window kernels.
+bool pick_fused_edge_step(const Elem& el, const Tuning& tn, const void* dZ, const void* V, const void* dV, int64_t N, int32_t L,
+                          int64_t C, int64_t v_bstride, const Offsets& offs, WinPick* pk) {
+  if (!el.f32_routes || tn.bwd_fused != 1 || L < kWinLmin || L > kWinLmax || !fused_step_width(el, C, N)) return false;
+  const int tgs = ceil_log2(C / el.vec), TR = 256 >> tgs;
   if (N < 2 * (int64_t)TR) return false;
   if (!aligned_to(dZ, 16) || !aligned_to(V, 16) || !aligned_to(dV, 16)) return false;
   if (v_bstride != 0 && v_bstride != N * C) return false;
-  int KN = 2;
-  for (int t = TR; t > 1; t >>= 1) ++KN;
-  if (KN > L) KN = L;
-  for (int k = 0; k < KN; ++k)
-    if (offs.v[k] != chord_off(k)) return false;
-  pk->tgs = tgs, pk->rows = 1, pk->nt = nt, pk->TR = TR, pk->KN = KN;
-  pk->tiles_full = (int)(N / TR), pk->ragged = (N % TR) != 0, pk->all_edge = true;
+  const int KN = near_links(TR, L, offs);
+  if (!KN) return false;
+  set_pick(pk, tgs, 1, 256, TR, KN, N);
+  pk->all_edge = true;
   return true;
 }
 
-// The fused dV + dW step (bwd_fused.h) applies to full tiles of rows of exactly 4 << tgs channels (fused_step_width), N a multiple of
-// the tile (256 >> tgs rows) and at least two tiles, chord near offsets, everything 16-byte aligned and chunk-clean.
-bool pick_fused_step(const Tuning& tn, const void* dZ, const void* W, const void* V, const void* dW, const void* dV, int64_t B, int64_t N,
-                     int32_t L, int64_t C, int64_t v_bstride, const Offsets& offs, WinPick* pk) {
+// The fused dV + dW step (bwd_fused.h, bwd_fused_bf16.h) applies to full tiles of rows of exactly el.vec << tgs channels
+// (fused_step_width), N a multiple of the tile (256 >> tgs rows) and at least two tiles, chord near offsets, every far offset a
+// multiple of the tile, all five operands 16-byte aligned and W / dW chunk-clean, a batch element's rows below 2^31 bytes.
+// Knob bwd_fused: 0 never, 1 where fused_step_auto says, 2 wherever it applies. (One pick for both element types: bf16's
+// was pick_fused_step_bf16.)
+bool pick_fused_step(const Elem& el, const Tuning& tn, const void* dZ, const void* W, const void* V, const void* dW, const void* dV,
+                     int64_t B, int64_t N, int32_t L, int64_t C, int64_t v_bstride, const Offsets& offs, WinPick* pk) {
   const int knob = tn.bwd_fused;
-  if (!knob || L < kWinLmin || L > kWinLmax || !fused_step_width(C, N)) return false;
-  const int tgs = C == 4 ? 0 : C == 8 ? 1 : C == 16 ? 2 : C == 32 ? 3 : C == 64 ? 4 : 5;
-  const int nt = 256;
-  const int TR = nt >> tgs;
+  if (!knob || L < kWinLmin || L > kWinLmax || !fused_step_width(el, C, N)) return false;
+  if (knob == 1 && !fused_step_auto(el, B, N, C)) return false;
+  const int tgs = ceil_log2(C / el.vec), TR = 256 >> tgs;
   if (N % TR != 0 || N < 2 * (int64_t)TR) return false;
   if (!aligned_to(dZ, 16) || !aligned_to(W, 16) || !aligned_to(V, 16) || !aligned_to(dW, 16) || !aligned_to(dV, 16)) return false;
-  if ((B * N * (int64_t)L) % 4 != 0 || (v_bstride != 0 && v_bstride != N * C)) return false;
-  int KN = 2;
-  for (int t = TR; t > 1; t >>= 1) ++KN;
-  if (KN > L) KN = L;
-  for (int k = 0; k < KN; ++k)
-    if (offs.v[k] != chord_off(k)) return false;
+  if ((B * N * (int64_t)L) % el.vec != 0 || (v_bstride != 0 && v_bstride != N * C)) return false;
+  const int KN = near_links(TR, L, offs);
+  if (!KN) return false;
   for (int k = KN; k < L; ++k)
     if (offs.v[k] % TR != 0) return false;  // far row blocks are TR-aligned (scalar block addresses in the kernel)
-  if (N * C * 4 >= ((int64_t)1 << 31)) return false;
-  pk->tgs = tgs, pk->rows = 1, pk->nt = nt, pk->TR = TR, pk->KN = KN;
-  pk->tiles_full = (int)(N / TR), pk->ragged = false, pk->all_edge = false;
+  if (N * C * el.bytes >= ((int64_t)1 << 31)) return false;
+  set_pick(pk, tgs, 1, 256, TR, KN, N);
+  pk->all_edge = false;
   return true;
+}
+
+// Interleaved fronts of the fused step (Geom::ileave): the shift, 0 = one front.
+// Two interleaved fronts per batch element (Geom::ileave, bwd_fused.h): tile t of the XCD's walk is row block
+// (t mod 2) tiles / 2 + t / 2, so the rows N / 2 apart that the longest link joins are in flight together. Round 6,
+// operands rotating as in the chain's backward (profiles/r06c_bwd_ileave2.log, us per step, one front / two): Order
+// shape (N = 16384, C = 8, B = 40) 41.1 / 39.2, N = 4096 x 32 channels 22.1 / 21.6, genome (N = 16384 x 32) 46.5 / 47.0
+// (noise); four and eight fronts equal two. In the training steps (r06c_step_ileave.log): Order 2.100 -> 2.074 ms,
+// genome 1.764 -> 1.734, IMDb (edge kernel: not applicable) unchanged. Auto: two fronts from N = 8192 on. (The forward
+// window kernel gains nothing from it at any shape — cfg2 25.8 / 26.0 us, genome 22.8 / 23.2 — and keeps one front:
+// profiles/r06c_fwd_fronts.log.)
+// Fronts and workgroups per CU: f32's rules (two fronts from N = 8192 on; no limit) kept unmeasured for bf16 unless the .md says otherwise
+int fused_fronts_shift(const Tuning& tn, int64_t N, int tiles_full) {
+  const int fronts = tn.bwd_fronts ? tn.bwd_fronts : (N >= 8192 ? 2 : 1);
+  int sh = 0;
+  while ((2 << sh) <= fronts) ++sh;
+  return sh > 0 && tiles_full % (1 << sh) == 0 ? sh : 0;
+}
+
+// Workgroups per CU of the f32 fused step, re-measured on the round-4 kernel with rotating operands (profiles/r04am_bwd_fused_wg_sweep.log, us per
+// step, what fits / three): 5120 tiles (N = 16384, C = 8, B = 40) 42.3 / 40.9; 8192 tiles (C = 32, B = 16) 51.0 / 49.6; 4096
+// tiles (N = 4096, C = 16, B = 64) 26.6 / 25.4; 2048 tiles 12.6 / 13.5 and 14.7 / 15.0: three from 4096 tiles on.
+// Rows of 64 / 128 channels (round 6, tiles of 16 / 8 rows; profiles/r06r_bwd_rows_wide.log, what fits / three / four):
+// N = 2048 x 64, B = 32: 17.4 / 17.3 / 15.9; N = 4096 x 64, B = 16: 17.4 / 17.3 / 16.3; N = 2000 x 128: 35.5 / 35.6 / 34.8;
+// N = 16384 x 64: 47.0 / 47.1 / 47.5 — four from 4096 tiles on. bf16: no limit (see fused_fronts_shift).
+int fused_wg_auto(const Elem& el, int64_t tiles_total, int tgs) {
+  return el.f32_routes && tiles_total >= 4096 ? (tgs >= 4 ? 4 : 3) : 0;
 }
 
 // A ragged last tile per sequence (N % TR != 0) runs on the EDGE instance. In a second launch of its own it costs a
@@ -345,15 +396,7 @@ bool ragged_in_one_launch(const Tuning& tn, bool ragged, int64_t B, int64_t N, i
   return ragged && tn.fwd_split == 1 && 4 * B * N * (L + 3 * C) <= (int64_t)300 * 1000 * 1000;
 }
 
-hipError_t launch_dwc(const WinPick& pk, int L, const BwdWinArgs& a) {
-  switch (pk.tgs) {
-    case 3: return launch_dw_chunk<3>(L, a);
-    case 4: return launch_dw_chunk<4>(L, a);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// Chunk-looping dW (bwd_dw_chunk.h), rows of >= 32 channels whose channel groups split into chunks of 8 (or 16) lanes:
+// Chunk-looping dW (bwd_dw_chunk.h, f32), rows of >= 32 channels whose channel groups split into chunks of 8 (or 16) lanes:
 // 256 threads x 1 row, so tiles of 32 (16) rows. Fills `pick` when the kernel applies.
 bool pick_dw_chunk(const Tuning& tn, const void* dW, int64_t B, int64_t N, int32_t L, int64_t C, const Offsets& offs, bool vec_ok,
                    WinPick* pick) {
@@ -366,97 +409,71 @@ bool pick_dw_chunk(const Tuning& tn, const void* dW, int64_t B, int64_t N, int32
   if (knob == 5 || (knob == 0 && CG % 16 == 0 && N % 32 != 0 && N % 16 == 0)) tgs = CG % 16 == 0 ? 4 : 3;
   const int TR = win_tile_rows(tgs, 1, 256);
   if (N < 2 * (int64_t)TR) return false;
-  int KN = 2;
-  for (int t = TR; t > 1; t >>= 1) ++KN;
-  if (KN > L) KN = L;
-  for (int k = 0; k < KN; ++k)
-    if (offs.v[k] != chord_off(k)) return false;  // near offsets are compile-time constants in this kernel
+  const int KN = near_links(TR, L, offs);
+  if (!KN) return false;
   if (N * C >= ((int64_t)1 << 31)) return false;                 // 32-bit element offsets inside a batch element
-  pick->tgs = tgs;
-  pick->rows = 1;
-  pick->nt = 256;
-  pick->TR = TR;
-  pick->KN = KN;
-  pick->tiles_full = (int)(N / TR);
-  pick->ragged = (N % TR) != 0;
+  set_pick(pick, tgs, 1, 256, TR, KN, N);
   pick->all_edge = ragged_in_one_launch(tn, pick->ragged, B, N, L, C) || !aligned_to(dW, 16) || ((N * (int64_t)L) % 4) != 0 || !tn.fwd_split;
   return true;
 }
 
-hipError_t launch_dw(const WinPick& pk, int L, const BwdWinArgs& a) {
-  switch (pk.tgs) {
-    case 0: return launch_dw_win<0>(pk.rows, L, a);
-    case 1: return launch_dw_win<1>(pk.rows, L, a);
-    case 2: return launch_dw_win<2>(pk.rows, L, a);
-    case 3: return launch_dw_win<3>(pk.rows, L, a);
-    case 4: return launch_dw_win<4>(pk.rows, L, a);
-    case 5: return launch_dw_win<5>(pk.rows, L, a);
-    case 6: return launch_dw_win<6>(pk.rows, L, a);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// Decide whether a window kernel applies (f32, vectorisable, chord-like near links); fills pick on success.
+// Decide whether a window kernel applies (vectorisable, chord-like near links); fills pick on success.
 // `W` is the flat [B,N,L] array the kernel copies in 16-byte chunks (W itself, or dW for the dW kernel).
-// `chunk_channels`: the kernel may split a row's channels over several workgroups (forward, dV) — then wide rows
+// `rows_pref`: 2 (forward, dV) or 1 (dW): the compiled rows per thread (fwd_window_launch.h).
+// `chunk_channels`: the kernel may split a row's channels over several workgroups (forward, dV) — then wide f32 rows
 // (C >= 64) use the wide-row configuration: 32-channel chunks, 1024 threads, 256-row tiles.
-bool pick_window(const Tuning& tn, const void* W, int64_t B, int64_t N, int32_t L, int64_t C, const Offsets& offs, bool vec_ok,
-                 WinPick* pick, int rows_pref, bool chunk_channels, int nt_pref = 0, bool forward = false) {
+// bf16 (was pick_window_bf16): no wide-row, four-row or 512-thread configuration; the same near-offset and alignment rules
+// with 8 elements per 16-byte chunk and 2-byte elements.
+bool pick_window(const Elem& el, const Tuning& tn, const void* W, int64_t B, int64_t N, int32_t L, int64_t C, const Offsets& offs,
+                 bool vec_ok, WinPick* pick, int rows_pref, bool chunk_channels, int nt_pref = 0, bool forward = false) {
   if (!vec_ok || L < kWinLmin || L > kWinLmax) return false;
-  const int64_t CG = C / 4;
-  int tgs = ceil_log2(CG) > kWinTgsMax ? kWinTgsMax : ceil_log2(CG);
+  const int64_t CG = C / el.vec;
+  int tgs = ceil_log2(CG) > el.tgs_max ? el.tgs_max : ceil_log2(CG);
   int nt = 256;
-  int rows = rows_pref;  // 2 (forward, dV) or 1 (dW): the compiled rows per thread (fwd_window_launch.h)
-  const int wide = tn.fwd_wide;
-  // Forward, rows of 64..256 channels, sequences up to 4096: 32-channel chunks on 1024-thread workgroups (256-row tiles: two
-  // far links at L = 12 instead of five to seven). With the scalar block addresses of round 4 they beat the whole-row tiles that
-  // rounds 1-3 measured faster: N = 2048, B = 32: C = 64 10.7 -> 9.0 us per step, C = 96 16.7 -> 14.3, C = 128 19.5 -> 18.3,
-  // C = 192 29.9 -> 25.7, C = 256 36.1 -> 33.9; N = 4096: +2..5 %; C = 512: equal; N = 16384, C = 64, B = 8: 23.7 -> 25.7 (slower)
-  // (profiles/r04ak_fwd_wide_rule_sweep.log). The backward kernels keep their configuration.
-  // Round 5, with operands rotating beyond the Infinity Cache as a training step has them (profiles/r05m_fwd_wide_mid.log, us per
-  // step, chunks / whole rows): N = 2048, C = 64: 10.5 / 11.8; N = 2048, C = 128: 20.8 / 22.0; N = 4096, C = 64: 21.7 / 22.6; C = 256:
-  // 21.2 / 21.9 — but ListOps' N = 2000, C = 128: 23.9 / 21.1: 2000 is no multiple of the 256-row chunk tile (every tile then takes the
-  // per-lane request form) and a multiple of the whole-row tile. So: chunks only where their tiles divide N or the whole-row tiles do not.
-  const int64_t tr_whole = win_tile_rows(tgs, rows, 256), tr_chunk = win_tile_rows(kWideTgs, rows, kWideThreads);
-  const bool auto_wide = forward && wide == 0 && CG >= 16 && CG <= 64 && N <= 4096 && (N % tr_chunk == 0 || N % tr_whole != 0);
-  if (chunk_channels && (wide == 1 || auto_wide) && CG >= 16 && N >= 2 * (int64_t)win_tile_rows(kWideTgs, rows, kWideThreads)) {
-    tgs = kWideTgs;  // 32-channel chunks on 1024-thread workgroups
-    nt = kWideThreads;
-  } else if (chunk_channels && wide == 2 && CG >= 16) {
-    tgs = kWideTgs;  // 32-channel chunks on 256-thread workgroups
-  } else if (nt_pref == kDvMidThreads && tgs <= kDvMidTgsMax && N >= 2 * (int64_t)win_tile_rows(tgs, 1, kDvMidThreads)) {
-    nt = kDvMidThreads;  // dV: 512 threads x 1 row
-    rows = 1;
-  }
-  // Forward, rows of 16..64 channels: four rows per thread (fwd_window_launch.h: win_rows4_compiled) where the four-row tile
-  // divides N, i.e. where its launches take the aligned request form; the per-lane form of other lengths (2^k + 1: LRA's
-  // CLS-token column) is faster on the smaller tile (N = 4097 x 32: 11.3 / 12.1 us, N = 1025: 6.9 / 7.2, two rows / four:
-  // profiles/r06k_fwd_rows_product.log). From N = 4096 on: below that the two forms are within 3 % of each other and the sign
-  // depends on how the step is driven (Pathfinder's shape, N = 1024 x 32: 6.32 / 6.13 us per step inside a chain, but 5.82 /
-  // 6.39 us per launch for the same step launched alone again and again under rocprofv3: r06m_fwd_rows_resident.log,
-  // r06z_bwd_summary.md of both collections).
-  if (forward && win_rows4_compiled(tgs, nt) && tn.fwd_rows != 2 && N >= 2 * (int64_t)win_tile_rows(tgs, 4, nt)) {
-    if (tn.fwd_rows == 4 || (N >= 4096 && N % win_tile_rows(tgs, 4, nt) == 0)) rows = 4;
+  int rows = rows_pref;
+  if (el.f32_routes) {
+    const int wide = tn.fwd_wide;
+    // Forward, rows of 64..256 channels, sequences up to 4096: 32-channel chunks on 1024-thread workgroups (256-row tiles: two
+    // far links at L = 12 instead of five to seven). With the scalar block addresses of round 4 they beat the whole-row tiles that
+    // rounds 1-3 measured faster: N = 2048, B = 32: C = 64 10.7 -> 9.0 us per step, C = 96 16.7 -> 14.3, C = 128 19.5 -> 18.3,
+    // C = 192 29.9 -> 25.7, C = 256 36.1 -> 33.9; N = 4096: +2..5 %; C = 512: equal; N = 16384, C = 64, B = 8: 23.7 -> 25.7 (slower)
+    // (profiles/r04ak_fwd_wide_rule_sweep.log). The backward kernels keep their configuration.
+    // Round 5, with operands rotating beyond the Infinity Cache as a training step has them (profiles/r05m_fwd_wide_mid.log, us per
+    // step, chunks / whole rows): N = 2048, C = 64: 10.5 / 11.8; N = 2048, C = 128: 20.8 / 22.0; N = 4096, C = 64: 21.7 / 22.6; C = 256:
+    // 21.2 / 21.9 — but ListOps' N = 2000, C = 128: 23.9 / 21.1: 2000 is no multiple of the 256-row chunk tile (every tile then takes the
+    // per-lane request form) and a multiple of the whole-row tile. So: chunks only where their tiles divide N or the whole-row tiles do not.
+    const int64_t tr_whole = win_tile_rows(tgs, rows, 256), tr_chunk = win_tile_rows(kWideTgs, rows, kWideThreads);
+    const bool auto_wide = forward && wide == 0 && CG >= 16 && CG <= 64 && N <= 4096 && (N % tr_chunk == 0 || N % tr_whole != 0);
+    if (chunk_channels && (wide == 1 || auto_wide) && CG >= 16 && N >= 2 * (int64_t)win_tile_rows(kWideTgs, rows, kWideThreads)) {
+      tgs = kWideTgs;  // 32-channel chunks on 1024-thread workgroups
+      nt = kWideThreads;
+    } else if (chunk_channels && wide == 2 && CG >= 16) {
+      tgs = kWideTgs;  // 32-channel chunks on 256-thread workgroups
+    } else if (nt_pref == kDvMidThreads && tgs <= kDvMidTgsMax && N >= 2 * (int64_t)win_tile_rows(tgs, 1, kDvMidThreads)) {
+      nt = kDvMidThreads;  // dV: 512 threads x 1 row
+      rows = 1;
+    }
+    // Forward, rows of 16..64 channels: four rows per thread (fwd_window_launch.h: win_rows4_compiled) where the four-row tile
+    // divides N, i.e. where its launches take the aligned request form; the per-lane form of other lengths (2^k + 1: LRA's
+    // CLS-token column) is faster on the smaller tile (N = 4097 x 32: 11.3 / 12.1 us, N = 1025: 6.9 / 7.2, two rows / four:
+    // profiles/r06k_fwd_rows_product.log). From N = 4096 on: below that the two forms are within 3 % of each other and the sign
+    // depends on how the step is driven (Pathfinder's shape, N = 1024 x 32: 6.32 / 6.13 us per step inside a chain, but 5.82 /
+    // 6.39 us per launch for the same step launched alone again and again under rocprofv3: r06m_fwd_rows_resident.log,
+    // r06z_bwd_summary.md of both collections).
+    if (forward && win_rows4_compiled(tgs, nt) && tn.fwd_rows != 2 && N >= 2 * (int64_t)win_tile_rows(tgs, 4, nt)) {
+      if (tn.fwd_rows == 4 || (N >= 4096 && N % win_tile_rows(tgs, 4, nt) == 0)) rows = 4;
+    }
   }
   const int TR = win_tile_rows(tgs, rows, nt);
   if (N < 2 * (int64_t)TR) return false;  // the window may wrap at most once
-  int KN = 2;                             // offsets 0, 1, 2, ..., 2^(KN-2) <= TR
-  for (int t = TR; t > 1; t >>= 1) ++KN;
-  if (KN > L) KN = L;
-  for (int k = 0; k < KN; ++k)
-    if (offs.v[k] != chord_off(k)) return false;  // near offsets are compile-time constants in the window kernels
-  pick->tgs = tgs;
-  pick->rows = rows;
-  pick->nt = nt;
-  pick->TR = TR;
-  pick->KN = KN;
-  pick->tiles_full = (int)(N / TR);
-  pick->ragged = (N % TR) != 0;
-  pick->aligned = (N % TR) == 0 && N * C * 4 < ((int64_t)1 << 31);
+  const int KN = near_links(TR, L, offs);
+  if (!KN) return false;
+  set_pick(pick, tgs, rows, nt, TR, KN, N);
+  pick->aligned = (N % TR) == 0 && N * C * el.bytes < ((int64_t)1 << 31);
   for (int k = KN; k < L; ++k)
     if (offs.v[k] % TR != 0) pick->aligned = false;
   const int TG = 1 << tgs;
-  pick->all_edge = (CG % TG) != 0 || !aligned_to(W, 16) || ((B * N * (int64_t)L) % 4) != 0 || !tn.fwd_split ||
+  pick->all_edge = (CG % TG) != 0 || !aligned_to(W, 16) || ((B * N * (int64_t)L) % el.vec) != 0 || !tn.fwd_split ||
                    ragged_in_one_launch(tn, pick->ragged, B, N, L, C);
   return true;
 }
@@ -464,10 +481,107 @@ bool pick_window(const Tuning& tn, const void* W, int64_t B, int64_t N, int32_t 
 // The dV window kernel's configuration for a shape.
 // default rows per thread (r01 sweep, us at cfg2): dV R=2 31.3 vs R=1 32.7; 512 threads x 1 row per thread instead of
 // 256 x 2 is the same tile at C <= 8 (r02 lab 28.65 vs 29.05 us at cfg2)
-bool pick_dv(const Tuning& tn, const void* W, int64_t B, int64_t N, int32_t L, int64_t C, const Offsets& offs, bool vec_ok, WinPick* pk) {
-  const int dvt = tn.dv_threads;
-  const int nt_dv = (dvt == 0 && C <= 8) ? kDvMidThreads : 0;
-  return pick_window(tn, W, B, N, L, C, offs, vec_ok, pk, 2, true, nt_dv);
+bool pick_dv(const Elem& el, const Tuning& tn, const void* W, int64_t B, int64_t N, int32_t L, int64_t C, const Offsets& offs,
+             bool vec_ok, WinPick* pk) {
+  const int nt_dv = (tn.dv_threads == 0 && C <= 8) ? kDvMidThreads : 0;
+  return pick_window(el, tn, W, B, N, L, C, offs, vec_ok, pk, 2, true, nt_dv);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// one plan per step
+// ------------------------------------------------------------------------------------------------------
+struct FwdPlan {
+  bool window;    // the LDS-window kernel of `pk`; else the generic kernel on `vec` elements per thread
+  bool refused;   // fwd_variant = 2 and the window kernel does not apply: a launch is PSF_E_TUNING
+  WinPick pk;
+  int vec;
+  int wg_per_cu;  // window kernel: FwdWinArgsT::wg_per_cu
+};
+
+FwdPlan plan_fwd(const Elem& el, const Tuning& tn, const void* W, const void* V, const void* res, const void* out, int64_t B,
+                 int64_t N, int32_t L, int64_t C, const Offsets& offs) {
+  FwdPlan p{};
+  const bool vec_ok = (C % el.vec == 0) && aligned_to(V, 16) && aligned_to(out, 16) && (!res || aligned_to(res, 16));
+  p.vec = vec_ok ? el.vec : 1;
+  p.window = el.window && tn.fwd_variant != 1 && pick_window(el, tn, W, B, N, L, C, offs, vec_ok, &p.pk, 2, true, 0, true);
+  p.refused = !p.window && tn.fwd_variant == 2;
+  if (!p.window) return p;
+  // Workgroups per CU. Measured (profiles/r01e_fwd_wg_per_cu.log, us per launch, 4 / 3 per CU): cfg2 (C = 8, 4096
+  // tiles) 27.6 / 27.0; the same at B = 40 (2560 tiles) 18.9 / 18.8; C = 32, B = 16: 24.5 / 24.8; N = 4096, C = 16:
+  // 8.9 / 9.2; 2 per CU: 30.0 at cfg2. Round 3, chains that keep every step's output (training; N = 16384, C = 8, no limit /
+  // three per CU, profiles/r03al_fwd_wg_limit_sweep.log): B = 16 (1024 tiles) 9.4 / 9.7; B = 24 13.5 / 13.2; B = 32 16.5 /
+  // 16.1; B = 40 19.9 / 19.0; B = 48 22.8 / 21.8. So: three for narrow rows on launches of >= 1536 tiles, no limit otherwise.
+  // Rows of 32 channels on launches of >= 8192 tiles (round 4, profiles/r04ai_fwd_mid_sweep.log, N = 16384, B = 64): 102.9 / 97.4;
+  // at B = 16 (4096 tiles) 22.6 / 22.7, N = 4096, B = 32: 11.2 / 11.6 — so three there too, from 8192 tiles on.
+  // Rows of 16 channels (same sweep script, us per step, what fits / three): 8192 tiles (N = 16384, B = 64) 45.9 / 44.3; 2048
+  // tiles (B = 16) 13.1 / 12.8; 1024 tiles (N = 4096, B = 32) 7.1 / 7.8: three from 2048 tiles on.
+  // bf16 (was fwd_window_bf16): these thresholds, keyed on TGS and tile count, are f32 measurements applied to bf16 unchanged —
+  // a bf16 channel group holds twice the channels and a bf16 tile twice the rows of the f32 configuration with the same TGS, so
+  // they describe other workloads here; not re-tuned for bf16.
+  const int knob = tn.fwd_wg_limit;
+  const int64_t tiles_total = B * (int64_t)(p.pk.tiles_full + (p.pk.ragged ? 1 : 0));
+  const bool three = p.pk.nt == 256 && ((p.pk.tgs <= 1 && tiles_total >= 1536) || (p.pk.tgs == 2 && tiles_total >= 2048) ||
+                                        (p.pk.tgs == 3 && tiles_total >= 8192));
+  p.wg_per_cu = knob == 0 ? (three ? 3 : 0) : (knob == 1 ? 0 : knob);
+  return p;
+}
+
+enum class Route { kNone, kGeneric, kWindow, kChunk };  // kNone: not asked for, or the fused step computes it
+enum class Fused { kNone, kAligned, kEdge };
+
+struct BwdPlan {
+  Fused fused;
+  WinPick fpk;            // fused step: its tiles, fronts shift (Geom::ileave) and workgroups per CU
+  int ileave, wg_per_cu;
+  Route dw, dv;           // otherwise, per gradient: kChunk (dW, f32), kWindow or kGeneric (on dw_vec / dv_vec elements per thread)
+  WinPick dwpk, dvpk;
+  bool dw_all_edge;       // (dV's is dvpk.all_edge)
+  int dw_vec, dv_vec;
+  bool refused;           // dw_variant = 2 and the chunk-looping dW kernel does not apply: a launch is PSF_E_TUNING
+};
+
+// The kernels of one backward step. Pointers may be nullptr (describe: taken as aligned); want_dw / want_dv say which
+// gradients the caller asks for.
+BwdPlan plan_bwd(const Elem& el, const Tuning& tn, const void* dZ, const void* W, const void* V, const void* dW, const void* dV,
+                 bool want_dw, bool want_dv, int64_t B, int64_t N, int32_t L, int64_t C, int64_t v_bstride, const Offsets& offs) {
+  BwdPlan p{};
+  const bool dw_ok = (C % el.vec == 0) && aligned_to(dZ, 16) && aligned_to(V, 16);
+  const bool dv_ok = (C % el.vec == 0) && aligned_to(dZ, 16) && aligned_to(dV, 16);
+  p.dw_vec = dw_ok ? el.vec : 1, p.dv_vec = dv_ok ? el.vec : 1;
+  p.dw = want_dw ? Route::kGeneric : Route::kNone, p.dv = want_dv ? Route::kGeneric : Route::kNone;
+  // LDS-window kernels (f32 and bf16; f64 takes the generic kernels)
+  if (!el.window || tn.bwd_variant == 1 || B < 1) return p;
+  if (want_dw && want_dv) {  // the fused step, aligned instance first
+    if (pick_fused_step(el, tn, dZ, W, V, dW, dV, B, N, L, C, v_bstride, offs, &p.fpk)) {
+      p.fused = Fused::kAligned;
+      p.ileave = fused_fronts_shift(tn, N, p.fpk.tiles_full);
+      p.wg_per_cu = tn.bwd_fused_wg_limit ? tn.bwd_fused_wg_limit : fused_wg_auto(el, B * (int64_t)p.fpk.tiles_full, p.fpk.tgs);
+    } else if (pick_fused_edge_step(el, tn, dZ, V, dV, N, L, C, v_bstride, offs, &p.fpk)) {
+      p.fused = Fused::kEdge;
+    }
+    if (p.fused != Fused::kNone) {
+      p.dw = p.dv = Route::kNone;
+      return p;
+    }
+  }
+  // dW before dV: dV's output is the next (earlier) step's dZ, read first thing by that step's kernels; writing
+  // it last leaves it cache-hot (dV 27.4 -> 26.9 us, dW 20.5 -> 20.4 us in the Order training step)
+  // default rows per thread (r01 sweep, us at cfg2): dV R=2 31.3 vs R=1 32.7; dW R=1 22.9 vs R=2 28.7
+  if (want_dw) {
+    if (el.f32_routes && tn.dw_variant != 1 && pick_dw_chunk(tn, dW, B, N, L, C, offs, dw_ok, &p.dwpk)) {
+      p.dw = Route::kChunk;
+      p.dw_all_edge = p.dwpk.all_edge;
+    } else {
+      p.refused = el.f32_routes && tn.dw_variant == 2;  // (planned on all the same: describe names what follows)
+      if (C / el.vec <= (1 << el.tgs_max) && pick_window(el, tn, dW, B, N, L, C, offs, dw_ok, &p.dwpk, 1, false)) {
+        p.dw = Route::kWindow;
+        // the dW tile store is chunk-clean only if every sequence starts on a 16-byte boundary
+        p.dw_all_edge = p.dwpk.all_edge || ((N * (int64_t)L) % el.vec) != 0;
+      }
+    }
+  }
+  if (want_dv && pick_dv(el, tn, W, B, N, L, C, offs, dv_ok, &p.dvpk)) p.dv = Route::kWindow;
+  return p;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -504,184 +618,6 @@ int window_launches(const Tuning& tn, const WinPick& pk, bool all_edge, int64_t 
   return PSF_OK;
 }
 
-int fwd_window_f32(const Tuning& tn, const WinPick& pk, const float* W, const float* V, const float* res, float* out, int64_t B,
-                   int64_t N, int32_t L, int64_t C, int64_t v_batch_stride, const Offsets& offs, hipStream_t s) {
-  FwdWinArgs a;
-  a.W = W;
-  a.V = V;
-  a.res = res;
-  a.out = out;
-  a.offs = offs;
-  a.w_total = B * N * (int64_t)L;
-  a.stream = s;
-  // Workgroups per CU. Measured (profiles/r01e_fwd_wg_per_cu.log, us per launch, 4 / 3 per CU): cfg2 (C = 8, 4096
-  // tiles) 27.6 / 27.0; the same at B = 40 (2560 tiles) 18.9 / 18.8; C = 32, B = 16: 24.5 / 24.8; N = 4096, C = 16:
-  // 8.9 / 9.2; 2 per CU: 30.0 at cfg2. Round 3, chains that keep every step's output (training; N = 16384, C = 8, no limit /
-  // three per CU, profiles/r03al_fwd_wg_limit_sweep.log): B = 16 (1024 tiles) 9.4 / 9.7; B = 24 13.5 / 13.2; B = 32 16.5 /
-  // 16.1; B = 40 19.9 / 19.0; B = 48 22.8 / 21.8. So: three for narrow rows on launches of >= 1536 tiles, no limit otherwise.
-  const int knob = tn.fwd_wg_limit;
-  const int64_t tiles_total = B * (int64_t)(pk.tiles_full + (pk.ragged ? 1 : 0));
-  // Rows of 32 channels on launches of >= 8192 tiles (round 4, profiles/r04ai_fwd_mid_sweep.log, N = 16384, B = 64): 102.9 / 97.4;
-  // at B = 16 (4096 tiles) 22.6 / 22.7, N = 4096, B = 32: 11.2 / 11.6 — so three there too, from 8192 tiles on.
-  // Rows of 16 channels (same sweep script, us per step, what fits / three): 8192 tiles (N = 16384, B = 64) 45.9 / 44.3; 2048
-  // tiles (B = 16) 13.1 / 12.8; 1024 tiles (N = 4096, B = 32) 7.1 / 7.8: three from 2048 tiles on.
-  const bool three = pk.nt == 256 && ((pk.tgs <= 1 && tiles_total >= 1536) || (pk.tgs == 2 && tiles_total >= 2048) ||
-                                      (pk.tgs == 3 && tiles_total >= 8192));
-  a.wg_per_cu = knob == 0 ? (three ? 3 : 0) : (knob == 1 ? 0 : knob);
-  return window_launches(tn, pk, pk.all_edge, B, N, L, C, v_batch_stride, true, &a.gm, &a.edge,
-                         [&] { return launch_win(pk, L, a); }, "chord_fwd_win launch");
-}
-
-// The bf16 window kernels' configuration (fwd_window_launch.h: kWinTgsMaxBf16): 16-byte groups of 8 channels, TGS 0..4 on
-// 256 threads x `rows` (forward and dV: 2, rows wider than 128 channels split into 128-channel chunks; dW: 1); no wide-row,
-// four-row or 512-thread configuration. Same near-offset and alignment rules as pick_window with 8 elements per 16-byte chunk
-// and 2-byte elements. `W` is the flat [B,N,L] array the kernel copies in 16-byte chunks (W, or dW for the dW kernel).
-bool pick_window_bf16(const Tuning& tn, const void* W, int64_t B, int64_t N, int32_t L, int64_t C, const Offsets& offs, bool vec_ok,
-                      WinPick* pick, int rows = 2) {
-  if (!vec_ok || L < kWinLmin || L > kWinLmax) return false;
-  const int64_t CG = C / 8;
-  const int tgs = ceil_log2(CG) > kWinTgsMaxBf16 ? kWinTgsMaxBf16 : ceil_log2(CG);
-  const int nt = 256;
-  const int TR = win_tile_rows(tgs, rows, nt);
-  if (N < 2 * (int64_t)TR) return false;  // the window may wrap at most once
-  int KN = 2;                             // offsets 0, 1, 2, ..., 2^(KN-2) <= TR
-  for (int t = TR; t > 1; t >>= 1) ++KN;
-  if (KN > L) KN = L;
-  for (int k = 0; k < KN; ++k)
-    if (offs.v[k] != chord_off(k)) return false;
-  pick->tgs = tgs;
-  pick->rows = rows;
-  pick->nt = nt;
-  pick->TR = TR;
-  pick->KN = KN;
-  pick->tiles_full = (int)(N / TR);
-  pick->ragged = (N % TR) != 0;
-  pick->aligned = (N % TR) == 0 && N * C * 2 < ((int64_t)1 << 31);
-  for (int k = KN; k < L; ++k)
-    if (offs.v[k] % TR != 0) pick->aligned = false;
-  const int TG = 1 << tgs;
-  pick->all_edge = (CG % TG) != 0 || !aligned_to(W, 16) || ((B * N * (int64_t)L) % 8) != 0 || !tn.fwd_split ||
-                   ragged_in_one_launch(tn, pick->ragged, B, N, L, C);
-  return true;
-}
-
-hipError_t launch_win_bf16(const WinPick& pk, int L, const FwdWinArgsT<__bf16>& a) {
-  switch (pk.tgs) {
-    case 0: return launch_fwd_win_bf16<0>(pk.rows, L, a);
-    case 1: return launch_fwd_win_bf16<1>(pk.rows, L, a);
-    case 2: return launch_fwd_win_bf16<2>(pk.rows, L, a);
-    case 3: return launch_fwd_win_bf16<3>(pk.rows, L, a);
-    case 4: return launch_fwd_win_bf16<4>(pk.rows, L, a);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-hipError_t launch_dw_bf16(const WinPick& pk, int L, const BwdWinArgsT<__bf16>& a) {
-  switch (pk.tgs) {
-    case 0: return launch_dw_win_bf16<0>(L, a);
-    case 1: return launch_dw_win_bf16<1>(L, a);
-    case 2: return launch_dw_win_bf16<2>(L, a);
-    case 3: return launch_dw_win_bf16<3>(L, a);
-    case 4: return launch_dw_win_bf16<4>(L, a);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-hipError_t launch_dv_bf16(const WinPick& pk, int L, const BwdWinArgsT<__bf16>& a) {
-  switch (pk.tgs) {
-    case 0: return launch_dv_win_bf16<0>(L, a);
-    case 1: return launch_dv_win_bf16<1>(L, a);
-    case 2: return launch_dv_win_bf16<2>(L, a);
-    case 3: return launch_dv_win_bf16<3>(L, a);
-    case 4: return launch_dv_win_bf16<4>(L, a);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-hipError_t launch_fused_step_bf16(int tgs, int L, const BwdWinArgsT<__bf16>& a) {
-  switch (tgs) {
-    case 0: return launch_bwd_fused_bf16<0>(L, a);
-    case 1: return launch_bwd_fused_bf16<1>(L, a);
-    case 2: return launch_bwd_fused_bf16<2>(L, a);
-    case 3: return launch_bwd_fused_bf16<3>(L, a);
-    case 4: return launch_bwd_fused_bf16<4>(L, a);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// The automatic route (bwd_fused = 1) of the bf16 fused step: only the widths and lengths where it measured faster than the two
-// window kernels by more than the run-to-run spread (profiles/bf16_bwd_fused_ab.md). Until a shape has been measured it stays on
-// the two kernels; bwd_fused = 2 takes the fused step wherever it applies.
-bool fused_step_auto_bf16(int64_t B, int64_t N, int64_t C) {
-  (void)B, (void)N, (void)C;
-  return false;
-}
-// Fronts and workgroups per CU: f32's rules (two fronts from N = 8192 on; no limit) kept unmeasured for bf16 unless the .md says otherwise
-int fused_fronts_auto_bf16(int64_t N) { return N >= 8192 ? 2 : 1; }
-int fused_wg_auto_bf16(int64_t tiles_total, int tgs) {
-  (void)tiles_total, (void)tgs;
-  return 0;
-}
-
-// The bf16 fused dV + dW step (bwd_fused_bf16.h): full tiles of rows of exactly 8 << tgs channels (8..128), N a multiple of the
-// tile (256 >> tgs rows) and at least two tiles, chord near offsets, every far offset a multiple of the tile, all five operands
-// 16-byte aligned and W / dW chunk-clean, a batch element's rows below 2^31 bytes. Knob bwd_fused: 0 never, 1 where the fused
-// step measured faster than the two window kernels (fused_step_auto_bf16), 2 wherever it applies. There is no bf16 edge
-// instance: ragged N, other far offsets and misaligned W / dW stay on the two window kernels.
-bool pick_fused_step_bf16(const Tuning& tn, const void* dZ, const void* W, const void* V, const void* dW, const void* dV, int64_t B,
-                          int64_t N, int32_t L, int64_t C, int64_t v_bstride, const Offsets& offs, WinPick* pk) {
-  const int knob = tn.bwd_fused;
-  if (!knob || L < kWinLmin || L > kWinLmax) return false;
-  if (C != 8 && C != 16 && C != 32 && C != 64 && C != 128) return false;
-  const int tgs = ceil_log2(C / 8);
-  const int nt = 256;
-  const int TR = nt >> tgs;
-  if (N % TR != 0 || N < 2 * (int64_t)TR) return false;
-  if (knob == 1 && !fused_step_auto_bf16(B, N, C)) return false;
-  if (!aligned_to(dZ, 16) || !aligned_to(W, 16) || !aligned_to(V, 16) || !aligned_to(dW, 16) || !aligned_to(dV, 16)) return false;
-  if ((B * N * (int64_t)L) % 8 != 0 || (v_bstride != 0 && v_bstride != N * C)) return false;
-  int KN = 2;
-  for (int t = TR; t > 1; t >>= 1) ++KN;
-  if (KN > L) KN = L;
-  for (int k = 0; k < KN; ++k)
-    if (offs.v[k] != chord_off(k)) return false;
-  for (int k = KN; k < L; ++k)
-    if (offs.v[k] % TR != 0) return false;  // far row blocks are TR-aligned (scalar block addresses in the kernel)
-  if (N * C * 2 >= ((int64_t)1 << 31)) return false;
-  pk->tgs = tgs, pk->rows = 1, pk->nt = nt, pk->TR = TR, pk->KN = KN;
-  pk->tiles_full = (int)(N / TR), pk->ragged = false, pk->all_edge = false;
-  return true;
-}
-
-// Interleaved fronts of the bf16 fused step (Geom::ileave): the shift, 0 = one front
-int fused_fronts_shift_bf16(const Tuning& tn, int64_t N, int tiles_full) {
-  const int fronts = tn.bwd_fronts ? tn.bwd_fronts : fused_fronts_auto_bf16(N);
-  int sh = 0;
-  while ((2 << sh) <= fronts) ++sh;
-  return sh > 0 && tiles_full % (1 << sh) == 0 ? sh : 0;
-}
-
-// bf16 forward step on the window kernel. Workgroups per CU: fwd_window_f32's thresholds, keyed on TGS and tile count, are
-// f32 measurements applied to bf16 unchanged — a bf16 channel group holds twice the channels and a bf16 tile twice the rows of
-// the f32 configuration with the same TGS, so they describe other workloads here; not re-tuned for bf16.
-int fwd_window_bf16(const Tuning& tn, const WinPick& pk, const __bf16* W, const __bf16* V, const __bf16* res, __bf16* out, int64_t B,
-                    int64_t N, int32_t L, int64_t C, int64_t v_batch_stride, const Offsets& offs, hipStream_t s) {
-  FwdWinArgsT<__bf16> a;
-  a.W = W;
-  a.V = V;
-  a.res = res;
-  a.out = out;
-  a.offs = offs;
-  a.w_total = B * N * (int64_t)L;
-  a.stream = s;
-  const int knob = tn.fwd_wg_limit;
-  const int64_t tiles_total = B * (int64_t)(pk.tiles_full + (pk.ragged ? 1 : 0));
-  const bool three = (pk.tgs <= 1 && tiles_total >= 1536) || (pk.tgs == 2 && tiles_total >= 2048) || (pk.tgs == 3 && tiles_total >= 8192);
-  a.wg_per_cu = knob == 0 ? (three ? 3 : 0) : (knob == 1 ? 0 : knob);
-  return window_launches(tn, pk, pk.all_edge, B, N, L, C, v_batch_stride, true, &a.gm, &a.edge,
-                         [&] { return launch_win_bf16(pk, L, a); }, "chord_fwd_win<bf16> launch", 8);
-}
-
 template <typename T>
 int fwd_impl(const Tuning& tn, const T* W, const T* V, const T* res, T* out, int64_t B, int64_t N, int32_t L, int64_t C,
              int64_t v_batch_stride, const int64_t* offsets, void* stream) {
@@ -695,28 +631,32 @@ int fwd_impl(const Tuning& tn, const T* W, const T* V, const T* res, T* out, int
   Offsets offs;
   make_offsets(N, L, offsets, &offs);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-
   constexpr int VECW = 16 / (int)sizeof(T);
-  const bool vec_ok =
-      (C % VECW == 0) && aligned_to(V, 16) && aligned_to(out, 16) && (!res || aligned_to(res, 16));
 
-  const int variant = tn.fwd_variant;
-  if constexpr (sizeof(T) == 4) {  // window kernels: f32 and bf16 (f64 exists for gradcheck)
-    WinPick pk;
-    if (variant != 1 && pick_window(tn, W, B, N, L, C, offs, vec_ok, &pk, 2, true, 0, true))
-      return fwd_window_f32(tn, pk, W, V, res, out, B, N, L, C, v_batch_stride, offs, s);
-  } else if constexpr (__is_same(T, __bf16)) {
-    WinPick pk;
-    if (variant != 1 && pick_window_bf16(tn, W, B, N, L, C, offs, vec_ok, &pk))
-      return fwd_window_bf16(tn, pk, W, V, res, out, B, N, L, C, v_batch_stride, offs, s);
+  const FwdPlan p = plan_fwd(elem_of((int)sizeof(T)), tn, W, V, res, out, B, N, L, C, offs);
+  if constexpr (sizeof(T) != 8) {
+    if (p.window) {
+      FwdWinArgsT<T> a;
+      a.W = W;
+      a.V = V;
+      a.res = res;
+      a.out = out;
+      a.offs = offs;
+      a.w_total = B * N * (int64_t)L;
+      a.stream = s;
+      a.wg_per_cu = p.wg_per_cu;
+      return window_launches(tn, p.pk, p.pk.all_edge, B, N, L, C, v_batch_stride, true, &a.gm, &a.edge,
+                             [&] { return launch_win(p.pk, L, a); },
+                             kIsBf16<T> ? "chord_fwd_win<bf16> launch" : "chord_fwd_win launch", VECW);
+    }
   }
-  if (variant == 2)
+  if (p.refused)
     return fail(PSF_E_TUNING, "fwd_variant=2 forced but the window kernel does not apply to N=%lld L=%d C=%lld",
                 (long long)N, (int)L, (long long)C);
 
   Geom gm;
-  if (int rc = generic_geom(tn, B, N, L, C, vec_ok ? VECW : 1, true, v_batch_stride, &gm)) return rc;
-  if (vec_ok)
+  if (int rc = generic_geom(tn, B, N, L, C, p.vec, true, v_batch_stride, &gm)) return rc;
+  if (p.vec != 1)
     hipLaunchKernelGGL((chord_fwd_generic_k<T, VECW>), dim3(gm.nblocks), dim3(kBlock), 0, s, W, V, res, out, gm, offs);
   else
     hipLaunchKernelGGL((chord_fwd_generic_k<T, 1>), dim3(gm.nblocks), dim3(kBlock), 0, s, W, V, res, out, gm, offs);
@@ -742,143 +682,56 @@ int bwd_impl(const Tuning& tn, const T* dZ, const T* W, const T* V, T* dW, T* dV
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   constexpr int VECW = 16 / (int)sizeof(T);
 
-  if constexpr (__is_same(T, __bf16)) {  // bf16: the fused step, else LDS-window dW / dV (no chunk-looping dW in bf16)
-    if (tn.bwd_variant != 1) {
-      const int64_t w_total = B * N * (int64_t)L;
-      WinPick pk;
-      if (dW && dV && pick_fused_step_bf16(tn, dZ, W, V, dW, dV, B, N, L, C, v_batch_stride, offs, &pk)) {
-        BwdWinArgsT<__bf16> a{dZ, W, dV, Geom{}, offs, w_total, false, s};
-        a.V2 = V;
-        a.out2 = dW;
-        a.wg_per_cu = tn.bwd_fused_wg_limit ? tn.bwd_fused_wg_limit : fused_wg_auto_bf16(B * (int64_t)pk.tiles_full, pk.tgs);
-        if (int rc = make_geom(tn, B, N, L, C, 8, pk.tgs, pk.TR, false, v_batch_stride, 0, pk.tiles_full, &a.gm)) return rc;
-        a.gm.ileave = fused_fronts_shift_bf16(tn, N, pk.tiles_full);
-        hipError_t e = launch_fused_step_bf16(pk.tgs, L, a);
-        if (e != hipSuccess) return fail_hip(e, "chord_bwd_fused<bf16>");
-        dW = nullptr;
-        dV = nullptr;
-      }
-      if (dW && C / 8 <= (1 << kWinTgsMaxBf16) &&
-          pick_window_bf16(tn, dW, B, N, L, C, offs, (C % 8 == 0) && aligned_to(dZ, 16) && aligned_to(V, 16), &pk, 1)) {
-        // the dW tile store is chunk-clean only if every sequence starts on a 16-byte boundary
-        const bool all_edge = pk.all_edge || ((N * (int64_t)L) % 8) != 0;
-        BwdWinArgsT<__bf16> a{dZ, V, dW, Geom{}, offs, w_total, false, s};
-        int rc = window_launches(tn, pk, all_edge, B, N, L, C, v_batch_stride, false, &a.gm, &a.edge,
-                                 [&] { return launch_dw_bf16(pk, L, a); }, "chord_dw_win<bf16>", 8);
-        if (rc) return rc;
-        dW = nullptr;
-      }
-      if (dV && pick_window_bf16(tn, W, B, N, L, C, offs, (C % 8 == 0) && aligned_to(dZ, 16) && aligned_to(dV, 16), &pk, 2)) {
-        BwdWinArgsT<__bf16> a{dZ, W, dV, Geom{}, offs, w_total, false, s};
-        int rc = window_launches(tn, pk, pk.all_edge, B, N, L, C, N * C, true, &a.gm, &a.edge,
-                                 [&] { return launch_dv_bf16(pk, L, a); }, "chord_dv_win<bf16>", 8);
-        if (rc) return rc;
-        dV = nullptr;
-      }
+  const BwdPlan p = plan_bwd(elem_of((int)sizeof(T)), tn, dZ, W, V, dW, dV, dW != nullptr, dV != nullptr, B, N, L, C, v_batch_stride, offs);
+  if (p.refused)
+    return fail(PSF_E_TUNING, "dw_variant=2 forced but the chunk-looping dW kernel does not apply to N=%lld L=%d C=%lld",
+                (long long)N, (int)L, (long long)C);
+  if constexpr (sizeof(T) != 8) {
+    constexpr bool bf = kIsBf16<T>;
+    const int64_t w_total = B * N * (int64_t)L;
+    if (p.fused != Fused::kNone) {
+      const bool edge = p.fused == Fused::kEdge;
+      BwdWinArgsT<T> a{dZ, W, dV, Geom{}, offs, w_total, edge, s};
+      a.V2 = V;
+      a.out2 = dW;
+      a.wg_per_cu = p.wg_per_cu;
+      if (!bf && !edge) a.ablate = tn.bwd_ablate;
+      if (int rc = make_geom(tn, B, N, L, C, VECW, p.fpk.tgs, p.fpk.TR, false, v_batch_stride, 0,
+                             p.fpk.tiles_full + (p.fpk.ragged ? 1 : 0), &a.gm))
+        return rc;
+      a.gm.ileave = p.ileave;
+      hipError_t e = launch_fused(edge, p.fpk.tgs, L, a);
+      if (e != hipSuccess) return fail_hip(e, bf ? "chord_bwd_fused<bf16>" : edge ? "chord_bwd_fused_edge" : "chord_bwd_fused");
     }
-  }
-  if constexpr (sizeof(T) == 4) {  // LDS-window kernels (f32; f64 takes the generic kernels). Whatever they handle is cleared below.
-    if (tn.bwd_variant != 1) {
-      const int64_t w_total = B * N * (int64_t)L;
-      const int TGmax = 1 << kWinTgsMax;
-      WinPick pk;
-      // default rows per thread (r01 sweep, us at cfg2): dV R=2 31.3 vs R=1 32.7; dW R=1 22.9 vs R=2 28.7
-      const int rows_dw = 1;
-      // dW before dV: dV's output is the next (earlier) step's dZ, read first thing by that step's kernels; writing
-      // it last leaves it cache-hot (dV 27.4 -> 26.9 us, dW 20.5 -> 20.4 us in the Order training step)
-      const int dwv = tn.dw_variant;
-      if (dW && dV && pick_fused_step(tn, dZ, W, V, dW, dV, B, N, L, C, v_batch_stride, offs, &pk)) {
-        BwdWinArgs a{dZ, W, dV, Geom{}, offs, w_total, false, s};
-        a.V2 = V;
-        a.out2 = dW;
-        // Workgroups per CU, re-measured on the round-4 kernel with rotating operands (profiles/r04am_bwd_fused_wg_sweep.log, us per
-        // step, what fits / three): 5120 tiles (N = 16384, C = 8, B = 40) 42.3 / 40.9; 8192 tiles (C = 32, B = 16) 51.0 / 49.6; 4096
-        // tiles (N = 4096, C = 16, B = 64) 26.6 / 25.4; 2048 tiles 12.6 / 13.5 and 14.7 / 15.0: three from 4096 tiles on.
-        // Rows of 64 / 128 channels (round 6, tiles of 16 / 8 rows; profiles/r06r_bwd_rows_wide.log, what fits / three / four):
-        // N = 2048 x 64, B = 32: 17.4 / 17.3 / 15.9; N = 4096 x 64, B = 16: 17.4 / 17.3 / 16.3; N = 2000 x 128: 35.5 / 35.6 / 34.8;
-        // N = 16384 x 64: 47.0 / 47.1 / 47.5 — four from 4096 tiles on.
-        a.wg_per_cu = tn.bwd_fused_wg_limit ? tn.bwd_fused_wg_limit
-                                            : (B * (int64_t)pk.tiles_full >= 4096 ? (pk.tgs >= 4 ? 4 : 3) : 0);
-        a.ablate = tn.bwd_ablate;
-        if (int rc = make_geom(tn, B, N, L, C, 4, pk.tgs, pk.TR, false, v_batch_stride, 0, pk.tiles_full, &a.gm)) return rc;
-        // Two interleaved fronts per batch element (Geom::ileave, bwd_fused.h): tile t of the XCD's walk is row block
-        // (t mod 2) tiles / 2 + t / 2, so the rows N / 2 apart that the longest link joins are in flight together. Round 6,
-        // operands rotating as in the chain's backward (profiles/r06c_bwd_ileave2.log, us per step, one front / two): Order
-        // shape (N = 16384, C = 8, B = 40) 41.1 / 39.2, N = 4096 x 32 channels 22.1 / 21.6, genome (N = 16384 x 32) 46.5 / 47.0
-        // (noise); four and eight fronts equal two. In the training steps (r06c_step_ileave.log): Order 2.100 -> 2.074 ms,
-        // genome 1.764 -> 1.734, IMDb (edge kernel: not applicable) unchanged. Auto: two fronts from N = 8192 on. (The forward
-        // window kernel gains nothing from it at any shape — cfg2 25.8 / 26.0 us, genome 22.8 / 23.2 — and keeps one front:
-        // profiles/r06c_fwd_fronts.log.)
-        {
-          const int fronts = tn.bwd_fronts ? tn.bwd_fronts : (N >= 8192 ? 2 : 1);
-          int sh = 0;
-          while ((2 << sh) <= fronts) ++sh;
-          if (sh > 0 && pk.tiles_full % (1 << sh) == 0) a.gm.ileave = sh;
-        }
-        hipError_t e = launch_fused_step(pk.tgs, L, a);
-        if (e != hipSuccess) return fail_hip(e, "chord_bwd_fused");
-        dW = nullptr;
-        dV = nullptr;
-      }
-      if (dW && dV && pick_fused_edge_step(tn, dZ, V, dV, N, L, C, v_batch_stride, offs, &pk)) {
-        BwdWinArgs a{dZ, W, dV, Geom{}, offs, w_total, true, s};
-        a.V2 = V;
-        a.out2 = dW;
-        if (int rc = make_geom(tn, B, N, L, C, 4, pk.tgs, pk.TR, false, v_batch_stride, 0, pk.tiles_full + (pk.ragged ? 1 : 0), &a.gm))
-          return rc;
-        hipError_t e = launch_fused_edge_step(pk.tgs, L, a);
-        if (e != hipSuccess) return fail_hip(e, "chord_bwd_fused_edge");
-        dW = nullptr;
-        dV = nullptr;
-      }
-      if (dW && dwv != 1 &&
-          pick_dw_chunk(tn, dW, B, N, L, C, offs, (C % 4 == 0) && aligned_to(dZ, 16) && aligned_to(V, 16), &pk)) {
-        BwdWinArgs a{dZ, V, dW, Geom{}, offs, w_total, false, s};
-        int rc = window_launches(tn, pk, pk.all_edge, B, N, L, C, v_batch_stride, false, &a.gm, &a.edge,
-                                 [&] { return launch_dwc(pk, L, a); }, "chord_dw_chunk");
-        if (rc) return rc;
-        dW = nullptr;
-      } else if (dW && dwv == 2) {
-        return fail(PSF_E_TUNING, "dw_variant=2 forced but the chunk-looping dW kernel does not apply to N=%lld L=%d C=%lld",
-                    (long long)N, (int)L, (long long)C);
-      }
-      if (dW && C / 4 <= TGmax &&
-          pick_window(tn, dW, B, N, L, C, offs, (C % 4 == 0) && aligned_to(dZ, 16) && aligned_to(V, 16), &pk,
-                      rows_dw, false)) {
-        // the dW tile store is chunk-clean only if every sequence starts on a 16-byte boundary
-        const bool all_edge = pk.all_edge || ((N * (int64_t)L) % 4) != 0;
-        BwdWinArgs a{dZ, V, dW, Geom{}, offs, w_total, false, s};
-        int rc = window_launches(tn, pk, all_edge, B, N, L, C, v_batch_stride, false, &a.gm, &a.edge,
-                                 [&] { return launch_dw(pk, L, a); }, "chord_dw_win");
-        if (rc) return rc;
-        dW = nullptr;
-      }
-      if (dV && pick_dv(tn, W, B, N, L, C, offs, (C % 4 == 0) && aligned_to(dZ, 16) && aligned_to(dV, 16), &pk)) {
-        BwdWinArgs a{dZ, W, dV, Geom{}, offs, w_total, false, s};
-        int rc = window_launches(tn, pk, pk.all_edge, B, N, L, C, N * C, true, &a.gm, &a.edge,
-                                 [&] { return launch_dv(pk, L, a); }, "chord_dv_win");
-        if (rc) return rc;
-        dV = nullptr;
-      }
+    if (p.dw == Route::kChunk || p.dw == Route::kWindow) {
+      BwdWinArgsT<T> a{dZ, V, dW, Geom{}, offs, w_total, false, s};
+      int rc = window_launches(tn, p.dwpk, p.dw_all_edge, B, N, L, C, v_batch_stride, false, &a.gm, &a.edge,
+                               [&] { return launch_dw(p.dw == Route::kChunk, p.dwpk, L, a); },
+                               bf ? "chord_dw_win<bf16>" : p.dw == Route::kChunk ? "chord_dw_chunk" : "chord_dw_win", VECW);
+      if (rc) return rc;
+    }
+    if (p.dv == Route::kWindow) {
+      BwdWinArgsT<T> a{dZ, W, dV, Geom{}, offs, w_total, false, s};
+      int rc = window_launches(tn, p.dvpk, p.dvpk.all_edge, B, N, L, C, N * C, true, &a.gm, &a.edge,
+                               [&] { return launch_dv(p.dvpk, L, a); }, bf ? "chord_dv_win<bf16>" : "chord_dv_win", VECW);
+      if (rc) return rc;
     }
   }
 
-  if (dV) {
-    const bool vec_ok = (C % VECW == 0) && aligned_to(dZ, 16) && aligned_to(dV, 16);
+  if (p.dv == Route::kGeneric) {
     Geom gm;
-    if (int rc = generic_geom(tn, B, N, L, C, vec_ok ? VECW : 1, true, N * C, &gm)) return rc;
-    if (vec_ok)
+    if (int rc = generic_geom(tn, B, N, L, C, p.dv_vec, true, N * C, &gm)) return rc;
+    if (p.dv_vec != 1)
       hipLaunchKernelGGL((chord_dv_generic_k<T, VECW>), dim3(gm.nblocks), dim3(kBlock), 0, s, dZ, W, dV, gm, offs);
     else
       hipLaunchKernelGGL((chord_dv_generic_k<T, 1>), dim3(gm.nblocks), dim3(kBlock), 0, s, dZ, W, dV, gm, offs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "chord_dv_generic launch");
   }
-  if (dW) {
-    const bool vec_ok = (C % VECW == 0) && aligned_to(dZ, 16) && aligned_to(V, 16);
+  if (p.dw == Route::kGeneric) {
     Geom gm;
-    if (int rc = generic_geom(tn, B, N, L, C, vec_ok ? VECW : 1, false, v_batch_stride, &gm)) return rc;
-    if (vec_ok)
+    if (int rc = generic_geom(tn, B, N, L, C, p.dw_vec, false, v_batch_stride, &gm)) return rc;
+    if (p.dw_vec != 1)
       hipLaunchKernelGGL((chord_dw_generic_k<T, VECW>), dim3(gm.nblocks), dim3(kBlock), 0, s, dZ, V, dW, gm, offs);
     else
       hipLaunchKernelGGL((chord_dw_generic_k<T, 1>), dim3(gm.nblocks), dim3(kBlock), 0, s, dZ, V, dW, gm, offs);
@@ -900,26 +753,32 @@ uint64_t chain_store_mask(T* const* out_steps, int32_t M) {
   return mask;
 }
 
-// ChainArgs / ChainArgsBf16 of a one-launch chain; vecw = channels per 16-byte group
-template <typename Args, typename T>
-void fill_chain_args(Args* a, const T* const* W_steps, const T* V0, T* const* out_steps, int32_t M, uint64_t store_mask, int64_t N,
-                     int64_t C, int vecw, int64_t v0_batch_stride, const ChainLdsPlan& plan, const Tuning& tn) {
-  for (int m = 0; m < kChainMaxSteps; ++m) {
-    a->W[m] = m < M ? W_steps[m] : nullptr;
-    a->out[m] = m < M ? out_steps[m] : nullptr;
-  }
-  a->store_mask = store_mask;
-  a->V0 = V0;
-  a->v0_bstride = v0_batch_stride;
-  a->M = M;
-  a->N = (int32_t)N;
-  a->C = (int32_t)C;
-  a->CG = (int32_t)(C / vecw);
-  a->chunks = plan.chunks;
-  a->xcd_remap = tn.xcd_remap && plan.chunks > 1 ? 1 : 0;  // (one workgroup per sequence shares nothing with its neighbours)
-}
-
-// Where the automatic route (chain_fused = 1) runs a bf16 chain in one launch: bf16's own measurements, not the f32 gate
+// Where the automatic route (chain_fused = 1) runs a chain in one launch; `few_kept`: at most two step results reach memory.
+// f32. Every workgroup of a sequence streams the sequence's whole W: with `chunks` workgroups per sequence W crosses
+// L2 -> CU `chunks` times and every output row is stored in `chunks` pieces. Past ~8 the per-step kernels win
+// (profiles/r03n_chain_train_sweep.log, us per chain one launch / per step: ListOps N = 2000, C = 128, 32 chunks:
+// 361 / 223; N = 2048, C = 64, 16 chunks: 184 / 119; Pathfinder C = 32, 4 chunks: 72 / 78). chain_fused = 2 forces it.
+// Round 4 (the kernel built without SLP packing, profiles/r04al_chain_fused*.log, us per step, per-step / one launch):
+// when only the last result is kept (inference: two alternating buffers) the one launch wins wherever it fits, wide rows
+// included — N = 2000, C = 128: 18.6 / 15.1; N = 1024, C = 1024: 20.1 / 10.4; N = 2048, C = 64: 9.0 / 8.4 — and when every
+// step is kept (training) it loses from 65536 elements per sequence on — N = 2048, C = 32: 6.9 / 10.3; C = 64: 10.2 / 17.2 —
+// and wins below — N = 1024, C = 32: 7.1 / 5.6; N = 2048, C = 8: 6.9 / 4.3.
+// Round 6: the workgroups of a sequence now share an XCD (fwd_chain_lds.h: W crosses the fabric once per sequence) — one
+// launch, blockIdx order / XCD-aware, us per step-equivalent (profiles/r06u_chain_lds_xcd.log): N = 2000 x 128: 17.3 / 13.4;
+// N = 2048 x 64: 9.5 / 6.8; Pathfinder 1024 x 32: 3.4 / 2.6; attention map 1024 x 1024: 9.8 / 8.9. With every step kept
+// (training) it now wins up to 65 536 elements per sequence and, for N <= 1024, up to 131 072 (per step / one launch,
+// r06u_chain_keep_sweep.log): 2048 x 32: 6.9 / 5.8; 1024 x 64: 6.7 / 4.0; 1024 x 128: 9.2 / 7.8; but 2048 x 64: 9.8 / 11.0;
+// 2000 x 64: 10.5 / 10.8; 2000 x 128: 20.9 / 23.2.
+// Later in round 6: 1057 <= N <= 2048 on launches of >= 256 workgroups run chord_chain_rows_k (two channel groups per
+// workgroup: half the W streams). us per step, per-step launches / one group / two groups (profiles/r06v_chain_lds8_ab.log; lds8 = this kernel's first name):
+// last kept: 2000 x 128: 19.3 / 13.5 / 8.0; 2048 x 64: 8.9 / 6.8 / 4.3; every step kept: 2000 x 128: 20.9 / 23.6 / 17.2;
+// 2048 x 64: 9.7 / 11.0 / 8.9; 2000 x 64: 10.6 / 10.8 / 8.2; 2000 x 256: 37.7 / 39.5 / 32.6 - so with that instance the one
+// launch also takes training chains (up to the 524 288 elements per sequence measured); ListOps training step 2.507 -> 2.476 ms.
+// 2113 <= N <= 4160 (the LRA text task, N = 4097 x 32, B = 32: 256 workgroups) run the same kernel with one channel group and
+// five rows per thread when only the last result is kept (profiles/r06v_chain_long_ab2.log, per-step / one launch):
+// 13.0 / 7.2 us per step; 4096 x 32: 11.8 / 6.5; 3000 x 32: 9.6 / 5.4; with every step kept the per-step kernels stay
+// (13.5 / 14.5), and below 256 workgroups too (B = 16: 7.4 / 6.6 last kept but 8.3 / 11.3 kept; C = 8: 6.4 / 6.6).
+// bf16 (was chain_bf16_gate): bf16's own measurements, not the f32 gate
 // (profiles/bf16_chain_ab.log, us per step, per-step launches / one launch, last result kept | every step kept):
 //   ListOps 2000 x 128 (rows_k G = 2, 256 workgroups): 12.2 / 5.9 | 13.0 / 6.8;  2048 x 64 (lds_k CC = 1): 6.6 / 3.6 | 7.3 / 4.2;
 //   Pathfinder 1024 x 32: 4.9 / 3.2 | 6.4 / 3.6;  attention map 1024 x 1024, broadcast eye: 9.8 / 6.3 | 11.0 / 6.7;
@@ -930,8 +789,32 @@ void fill_chain_args(Args* a, const T* const* W_steps, const T* V0, T* const* ou
 // 832 threads at B = 32 — half the CUs idle: 9.3 / 9.0 | 10.0 / 9.6, inside the rounds' spread when the last result is kept;
 // B = 16: 6.0 / 8.9 | 6.4 / 9.5, a loss. No bf16 launch of that instance with >= 256 workgroups has been measured, so it
 // is never automatic (chain_fused = 2 with chain_cc = 2 runs it).
-bool chain_bf16_gate(const ChainLdsPlan& plan, int64_t N, int64_t C) {
-  return plan.big != 2 && N * C <= 1048576;
+bool chain_gate(const Elem& el, const ChainLdsPlan& plan, int64_t N, int64_t C, bool few_kept) {
+  if (el.bytes == 2) return plan.big != 2 && N * C <= 1048576;
+  return few_kept || N * C <= 65536 || (N <= 1024 && N * C <= 131072) || (plan.big == 1 && N * C <= 524288);
+}
+
+struct ChainPlan {
+  bool one_launch;  // short sequences: the whole chain in ONE launch with the sequence's X slice resident in LDS (`lds`)
+  bool grid_ok;     // ... whose B * chunks workgroups fit a grid
+  ChainLdsPlan lds;
+};
+
+// The one launch needs C a multiple of the 16-byte group, V0 and every stored result 16-byte aligned, and W rows that whole
+// aligned dwords cover: a 4-byte-aligned W, or in bf16 (ceil(L / 2) dwords per row) any 2-byte-aligned W for odd L. Anything
+// else takes the per-step launches. W_steps == nullptr (describe): operands taken as aligned.
+template <typename T>
+ChainPlan plan_chain(const Elem& el, const Tuning& tn, const T* const* W_steps, const T* V0, T* const* out_steps, int32_t M,
+                     bool few_kept, int64_t B, int64_t N, int32_t L, int64_t C) {
+  ChainPlan p{};
+  const int cf = tn.chain_fused;
+  bool ok = el.window && cf && M >= 2 && M <= kChainMaxSteps && B >= 1 && plan_chain_lds(N, C, L, M, &p.lds, tn.chain_cc, B, el.bytes) &&
+            (cf == 2 || chain_gate(el, p.lds, N, C, few_kept)) && aligned_to(V0, 16);
+  const size_t w_align = el.bytes == 2 && L % 2 ? 2 : 4;
+  for (int m = 0; ok && W_steps && m < M; ++m) ok = aligned_to(W_steps[m], w_align) && aligned_to(out_steps[m], 16);
+  p.one_launch = ok;
+  p.grid_ok = ok && B * (int64_t)p.lds.chunks <= 0x7fffffff;
+  return p;
 }
 
 template <typename T>
@@ -950,69 +833,36 @@ int chain_impl(Tuning tn, const T* const* W_steps, const T* V0, T* const* out_st
       return fail(PSF_E_ALIAS, "step %d: out aliases the step's input", m);
   }
 
-  if constexpr (sizeof(T) == 4) {
-    // Short sequences: the whole chain in ONE launch with the sequence's X slice resident in LDS.
-    ChainLdsPlan plan;
-    // Every workgroup of a sequence streams the sequence's whole W: with `chunks` workgroups per sequence W crosses
-    // L2 -> CU `chunks` times and every output row is stored in `chunks` pieces. Past ~8 the per-step kernels win
-    // (profiles/r03n_chain_train_sweep.log, us per chain one launch / per step: ListOps N = 2000, C = 128, 32 chunks:
-    // 361 / 223; N = 2048, C = 64, 16 chunks: 184 / 119; Pathfinder C = 32, 4 chunks: 72 / 78). chain_fused = 2 forces it.
-    // Round 4 (the kernel built without SLP packing, profiles/r04al_chain_fused*.log, us per step, per-step / one launch):
-    // when only the last result is kept (inference: two alternating buffers) the one launch wins wherever it fits, wide rows
-    // included — N = 2000, C = 128: 18.6 / 15.1; N = 1024, C = 1024: 20.1 / 10.4; N = 2048, C = 64: 9.0 / 8.4 — and when every
-    // step is kept (training) it loses from 65536 elements per sequence on — N = 2048, C = 32: 6.9 / 10.3; C = 64: 10.2 / 17.2 —
-    // and wins below — N = 1024, C = 32: 7.1 / 5.6; N = 2048, C = 8: 6.9 / 4.3.
-    // Round 6: the workgroups of a sequence now share an XCD (fwd_chain_lds.h: W crosses the fabric once per sequence) — one
-    // launch, blockIdx order / XCD-aware, us per step-equivalent (profiles/r06u_chain_lds_xcd.log): N = 2000 x 128: 17.3 / 13.4;
-    // N = 2048 x 64: 9.5 / 6.8; Pathfinder 1024 x 32: 3.4 / 2.6; attention map 1024 x 1024: 9.8 / 8.9. With every step kept
-    // (training) it now wins up to 65 536 elements per sequence and, for N <= 1024, up to 131 072 (per step / one launch,
-    // r06u_chain_keep_sweep.log): 2048 x 32: 6.9 / 5.8; 1024 x 64: 6.7 / 4.0; 1024 x 128: 9.2 / 7.8; but 2048 x 64: 9.8 / 11.0;
-    // 2000 x 64: 10.5 / 10.8; 2000 x 128: 20.9 / 23.2.
-    // Later in round 6: 1057 <= N <= 2048 on launches of >= 256 workgroups run chord_chain_rows_k (two channel groups per
-    // workgroup: half the W streams). us per step, per-step launches / one group / two groups (profiles/r06v_chain_lds8_ab.log; lds8 = this kernel's first name):
-    // last kept: 2000 x 128: 19.3 / 13.5 / 8.0; 2048 x 64: 8.9 / 6.8 / 4.3; every step kept: 2000 x 128: 20.9 / 23.6 / 17.2;
-    // 2048 x 64: 9.7 / 11.0 / 8.9; 2000 x 64: 10.6 / 10.8 / 8.2; 2000 x 256: 37.7 / 39.5 / 32.6 - so with that instance the one
-    // launch also takes training chains (up to the 524 288 elements per sequence measured); ListOps training step 2.507 -> 2.476 ms.
-    // 2113 <= N <= 4160 (the LRA text task, N = 4097 x 32, B = 32: 256 workgroups) run the same kernel with one channel group and
-    // five rows per thread when only the last result is kept (profiles/r06v_chain_long_ab2.log, per-step / one launch):
-    // 13.0 / 7.2 us per step; 4096 x 32: 11.8 / 6.5; 3000 x 32: 9.6 / 5.4; with every step kept the per-step kernels stay
-    // (13.5 / 14.5), and below 256 workgroups too (B = 16: 7.4 / 6.6 last kept but 8.3 / 11.3 kept; C = 8: 6.4 / 6.6).
-    const int cf = tn.chain_fused;
+  if constexpr (sizeof(T) != 8) {  // the one launch: f32 (fwd_chain_lds.h) and bf16 (fwd_chain_lds_bf16.h: 8 channels per
+                                   // 16-byte LDS slot, bit-identical to the per-step bf16 kernels)
     const uint64_t store_mask = M <= kChainMaxSteps ? chain_store_mask(out_steps, M) : ~(uint64_t)0;
-    const bool few_kept = __builtin_popcountll(store_mask) <= 2;  // step results that reach memory
-    bool ok = cf && M >= 2 && M <= kChainMaxSteps && B >= 1 && plan_chain_lds(N, C, L, M, &plan, tn.chain_cc, B) &&
-              (cf == 2 || few_kept || N * C <= 65536 || (N <= 1024 && N * C <= 131072) || (plan.big == 1 && N * C <= 524288)) &&
-              aligned_to(V0, 16) && B * (int64_t)plan.chunks <= 0x7fffffff;
-    for (int m = 0; ok && m < M; ++m) ok = aligned_to(W_steps[m], 4) && aligned_to(out_steps[m], 16);
-    if (ok) {
+    const ChainPlan p = plan_chain(elem_of((int)sizeof(T)), tn, W_steps, V0, out_steps, M, __builtin_popcountll(store_mask) <= 2, B, N, L, C);
+    if (p.one_launch && p.grid_ok) {
       if (int rc = check_dims(B, N, L, C, v0_batch_stride)) return rc;
-      ChainArgs a;
-      fill_chain_args(&a, W_steps, V0, out_steps, M, store_mask, N, C, 4, v0_batch_stride, plan, tn);
+      std::conditional_t<kIsBf16<T>, ChainArgsBf16, ChainArgs> a;
+      for (int m = 0; m < kChainMaxSteps; ++m) {
+        a.W[m] = m < M ? W_steps[m] : nullptr;
+        a.out[m] = m < M ? out_steps[m] : nullptr;
+      }
+      a.store_mask = store_mask;
+      a.V0 = V0;
+      a.v0_bstride = v0_batch_stride;
+      a.M = M;
+      a.N = (int32_t)N;
+      a.C = (int32_t)C;
+      a.CG = (int32_t)(C / (16 / (int)sizeof(T)));
+      a.chunks = p.lds.chunks;
+      a.xcd_remap = tn.xcd_remap && p.lds.chunks > 1 ? 1 : 0;  // (one workgroup per sequence shares nothing with its neighbours)
       Offsets offs;
       make_offsets(N, L, offsets, &offs);
-      hipError_t e = launch_chain_lds(plan, L, use_residual != 0, a, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
-      if (e != hipSuccess) return fail_hip(e, "chord_chain_lds launch");
-      return PSF_OK;
-    }
-  } else if constexpr (__is_same(T, __bf16)) {
-    // The same one launch in bf16 (fwd_chain_lds_bf16.h: 8 channels per 16-byte LDS slot, bit-identical to the per-step bf16
-    // kernels). Needs C % 8 == 0, V0 and every stored result 16-byte aligned, and W rows that ceil(L / 2) aligned dwords
-    // cover: any 2-byte-aligned W for odd L, a 4-byte-aligned one for even L. Anything else takes the per-step launches.
-    // The gate is bf16's own (chain_bf16_gate above).
-    ChainLdsPlan plan;
-    const int cf = tn.chain_fused;
-    const uint64_t store_mask = M <= kChainMaxSteps ? chain_store_mask(out_steps, M) : ~(uint64_t)0;
-    bool ok = cf && M >= 2 && M <= kChainMaxSteps && B >= 1 && plan_chain_lds(N, C, L, M, &plan, tn.chain_cc, B, 2) &&
-              (cf == 2 || chain_bf16_gate(plan, N, C)) && aligned_to(V0, 16) && B * (int64_t)plan.chunks <= 0x7fffffff;
-    for (int m = 0; ok && m < M; ++m) ok = aligned_to(W_steps[m], L % 2 ? 2 : 4) && aligned_to(out_steps[m], 16);
-    if (ok) {
-      if (int rc = check_dims(B, N, L, C, v0_batch_stride)) return rc;
-      ChainArgsBf16 a;
-      fill_chain_args(&a, W_steps, V0, out_steps, M, store_mask, N, C, 8, v0_batch_stride, plan, tn);
-      Offsets offs;
-      make_offsets(N, L, offsets, &offs);
-      hipError_t e = launch_chain_lds_bf16(plan, L, use_residual != 0, a, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
-      if (e != hipSuccess) return fail_hip(e, "chord_chain_lds<bf16> launch");
+      hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+      if constexpr (kIsBf16<T>) {
+        hipError_t e = launch_chain_lds_bf16(p.lds, L, use_residual != 0, a, offs, (int)B, s);
+        if (e != hipSuccess) return fail_hip(e, "chord_chain_lds<bf16> launch");
+      } else {
+        hipError_t e = launch_chain_lds(p.lds, L, use_residual != 0, a, offs, (int)B, s);
+        if (e != hipSuccess) return fail_hip(e, "chord_chain_lds launch");
+      }
       return PSF_OK;
     }
   }
@@ -1029,6 +879,70 @@ int chain_impl(Tuning tn, const T* const* W_steps, const T* V0, T* const* out_st
   return PSF_OK;
 }
 
+// The backward chain in one library call (K = float or __bf16). f32 runs the one-launch kernel where it fits
+// (bwd_chain_lds.h; there is no one-launch bf16 backward kernel). Otherwise the M per-step launches of psf_chord_spmm_bwd_*
+// (the fused step where it applies), the gradient handed from dX_steps[m] to the next step, and ONE psf_sum_tensors_* pass over
+// the residual terms at the end — ((g_M + g_{M-1}) + ... + g_1) + g_0, in bf16 summed in f32 and rounded once: what the
+// caller's loop (chord.py) did, without M trips through its language's FFI.
+template <typename K>
+int chain_bwd_impl(const K* dOut, const K* const* W_steps, const K* V0, const K* const* X_steps, K* const* dW_steps, K* dV0,
+                   K* const* dX_steps, int32_t M, int32_t use_residual, int64_t B, int64_t N, int32_t L, int64_t C,
+                   const int64_t* offsets, void* stream) {
+  constexpr int VECW = 16 / (int)sizeof(K);
+  if (M < 1) return fail(PSF_E_SHAPE, "M must be >= 1");
+  if (!dOut || !W_steps || !V0 || !X_steps || !dW_steps || !dV0) return fail(PSF_E_NULL, "a required pointer is NULL");
+  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
+  const Tuning tn = snapshot();
+  if (!tn.chain_bwd_fused) return PSF_E_UNSUPPORTED;  // (knob off: the caller runs the steps itself)
+  const bool one_launch = !kIsBf16<K> && chain_bwd_lds_fits(N, C, L, M);
+  // the per-step path inside the library needs the M gradient buffers and, with the residual, psf_sum_tensors_*'s limits
+  if (!one_launch && (!dX_steps || (use_residual && (M + 1 > 32 || (B * N * C) % VECW != 0)))) return PSF_E_UNSUPPORTED;
+  if (B == 0) return PSF_OK;
+  for (int m = 0; m < M; ++m) {
+    const K* x = m == 0 ? V0 : X_steps[m];
+    if (!W_steps[m] || !x || !dW_steps[m]) return fail(PSF_E_NULL, "step %d: NULL pointer", m);
+    if (dW_steps[m] == W_steps[m]) return fail(PSF_E_ALIAS, "step %d: dW aliases W", m);
+    if (!one_launch && !dX_steps[m]) return fail(PSF_E_NULL, "step %d: dX_steps[m] is NULL", m);
+  }
+  if constexpr (!kIsBf16<K>) {
+    if (one_launch) {
+      if (B > 0x7fffffff) return fail(PSF_E_SHAPE, "B too large");
+      ChainBwdArgs a;
+      for (int m = 0; m < M; ++m) {
+        const float* x = m == 0 ? V0 : X_steps[m];
+        if (!aligned_to(W_steps[m], 4) || !aligned_to(dW_steps[m], 4) || !aligned_to(x, 16))
+          return fail(PSF_E_ALIGN, "step %d: W / dW must be 4-byte, X 16-byte aligned", m);
+        a.W[m] = W_steps[m], a.X[m] = x, a.dW[m] = dW_steps[m];
+      }
+      for (int m = M; m < kChainMaxSteps; ++m) a.W[m] = nullptr, a.X[m] = nullptr, a.dW[m] = nullptr;
+      if (!aligned_to(dOut, 16) || !aligned_to(dV0, 16)) return fail(PSF_E_ALIGN, "dOut and dV0 must be 16-byte aligned");
+      a.dOut = dOut, a.dV0 = dV0, a.M = M, a.N = (int32_t)N, a.C = (int32_t)C;
+      Offsets offs;
+      make_offsets(N, L, offsets, &offs);
+      hipError_t e = launch_chain_bwd_lds(L, (int)(C / 4), use_residual != 0, a, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
+      if (e != hipSuccess) return fail_hip(e, "chord_chain_bwd_lds launch");
+      return PSF_OK;
+    }
+  }
+  const K* g = dOut;
+  const K* terms[kChainMaxSteps + 1];
+  int nterms = 0;
+  for (int m = M - 1; m >= 0; --m) {
+    if (use_residual) terms[nterms++] = g;
+    K* dx = (m == 0 && !use_residual) ? dV0 : dX_steps[m];
+    if (int rc = bwd_impl<K>(tn, g, W_steps[m], m == 0 ? V0 : X_steps[m], dW_steps[m], dx, B, N, L, C, N * C, offsets, stream))
+      return rc;
+    g = dx;
+  }
+  if (use_residual) {
+    terms[nterms++] = g;  // ((g_M + g_{M-1}) + ... + g_1) + g_0
+    if constexpr (kIsBf16<K>)
+      return psf_sum_tensors_bf16(reinterpret_cast<const uint16_t* const*>(terms), nterms, B * N * C, reinterpret_cast<uint16_t*>(dV0), stream);
+    else
+      return psf_sum_tensors_f32(terms, nterms, B * N * C, dV0, stream);
+  }
+  return PSF_OK;
+}
 
 // ------------------------------------------------------------------------------------------------------
 // the mixer with W computed inside the step (fwd_mlp_step.h)
@@ -1060,37 +974,26 @@ bool plan_mixer(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, in
   if (tgs <= kMlpStepTgsMax) {
     const int TR = mlp_step_tile_rows(tgs);
     if (N >= 2 * (int64_t)TR) {  // the window may wrap at most once
-      int KN = 2;
-      for (int t = TR; t > 1; t >>= 1) ++KN;
-      if (KN > L) KN = L;
       Offsets offs;
       make_offsets(N, L, nullptr, &offs);
-      bool chord = true;
-      for (int k = 0; k < KN; ++k) chord = chord && offs.v[k] == chord_off(k);  // near offsets are compile-time constants there
-      if (chord) mp->step_ok = true, mp->tgs = tgs, mp->TR = TR, mp->KN = KN;
+      const int KN = near_links(TR, L, offs);
+      if (KN) mp->step_ok = true, mp->tgs = tgs, mp->TR = TR, mp->KN = KN;
     }
   }
   return mp->step_ok || mp->lds_ok;
 }
 
-hipError_t launch_g(int tgs, const FwdMlpArgs& a) {
-  switch (tgs) {
-    case 0: return launch_mixer_g<0>(a);
-    case 1: return launch_mixer_g<1>(a);
-    case 2: return launch_mixer_g<2>(a);
-    case 3: return launch_mixer_g<3>(a);
-    default: return hipErrorInvalidValue;
-  }
+// psf_describe_*: argument checks, and the name of a window-kernel instance
+int describe_args(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_bytes, bool f64, const char* buf, int32_t cap) {
+  if (!buf || cap < 1) return fail(PSF_E_NULL, "buf is NULL");
+  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
+  if (elem_bytes != 2 && elem_bytes != 4 && !(f64 && elem_bytes == 8))
+    return fail(PSF_E_SHAPE, f64 ? "elem_bytes must be 2 (bf16), 4 or 8" : "elem_bytes must be 2 (bf16) or 4");
+  return PSF_OK;
 }
 
-hipError_t launch_mlp_step(int tgs, int L, const FwdMlpArgs& a) {
-  switch (tgs) {
-    case 0: return launch_fwd_mlp<0>(L, a);
-    case 1: return launch_fwd_mlp<1>(L, a);
-    case 2: return launch_fwd_mlp<2>(L, a);
-    case 3: return launch_fwd_mlp<3>(L, a);
-    default: return hipErrorInvalidValue;
-  }
+void print_win(char* buf, size_t cap, const char* kernel, const Elem& el, int32_t L, const WinPick& pk) {
+  snprintf(buf, cap, "%s<%s,L=%d,TG=%d,R=%d,NT=%d>", kernel, el.name, (int)L, 1 << pk.tgs, pk.rows, pk.nt);
 }
 
 }  // namespace
@@ -1227,96 +1130,17 @@ int psf_chord_chain_bwd_supported(int64_t N, int32_t L, int64_t C, int32_t M) {
 int psf_chord_chain_bwd_f32(const float* dOut, const float* const* W_steps, const float* V0, const float* const* X_steps,
                             float* const* dW_steps, float* dV0, float* const* dX_steps, int32_t M, int32_t use_residual,
                             int64_t B, int64_t N, int32_t L, int64_t C, const int64_t* offsets, void* stream) {
-  if (M < 1) return fail(PSF_E_SHAPE, "M must be >= 1");
-  if (!dOut || !W_steps || !V0 || !X_steps || !dW_steps || !dV0) return fail(PSF_E_NULL, "a required pointer is NULL");
-  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
-  if (!g_chain_bwd_fused.load()) return PSF_E_UNSUPPORTED;  // (knob off: the caller runs the steps itself)
-  const bool one_launch = chain_bwd_lds_fits(N, C, L, M);
-  // the per-step path inside the library needs the M gradient buffers and, with the residual, psf_sum_tensors_f32's limits
-  if (!one_launch && (!dX_steps || (use_residual && (M + 1 > 32 || (B * N * C) % 4 != 0)))) return PSF_E_UNSUPPORTED;
-  if (B == 0) return PSF_OK;
-  for (int m = 0; m < M; ++m) {
-    const float* x = m == 0 ? V0 : X_steps[m];
-    if (!W_steps[m] || !x || !dW_steps[m]) return fail(PSF_E_NULL, "step %d: NULL pointer", m);
-    if (dW_steps[m] == W_steps[m]) return fail(PSF_E_ALIAS, "step %d: dW aliases W", m);
-    if (!one_launch && !dX_steps[m]) return fail(PSF_E_NULL, "step %d: dX_steps[m] is NULL", m);
-  }
-  if (one_launch) {
-    if (B > 0x7fffffff) return fail(PSF_E_SHAPE, "B too large");
-    ChainBwdArgs a;
-    for (int m = 0; m < M; ++m) {
-      const float* x = m == 0 ? V0 : X_steps[m];
-      if (!aligned_to(W_steps[m], 4) || !aligned_to(dW_steps[m], 4) || !aligned_to(x, 16))
-        return fail(PSF_E_ALIGN, "step %d: W / dW must be 4-byte, X 16-byte aligned", m);
-      a.W[m] = W_steps[m], a.X[m] = x, a.dW[m] = dW_steps[m];
-    }
-    for (int m = M; m < kChainMaxSteps; ++m) a.W[m] = nullptr, a.X[m] = nullptr, a.dW[m] = nullptr;
-    if (!aligned_to(dOut, 16) || !aligned_to(dV0, 16)) return fail(PSF_E_ALIGN, "dOut and dV0 must be 16-byte aligned");
-    a.dOut = dOut, a.dV0 = dV0, a.M = M, a.N = (int32_t)N, a.C = (int32_t)C;
-    Offsets offs;
-    make_offsets(N, L, offsets, &offs);
-    hipError_t e = launch_chain_bwd_lds(L, (int)(C / 4), use_residual != 0, a, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(e, "chord_chain_bwd_lds launch");
-    return PSF_OK;
-  }
-  // M per-step launches (the kernels psf_chord_spmm_bwd_f32 runs), the gradient handed from buffer to buffer, and ONE pass
-  // over the residual terms at the end: what the caller's loop did, without M trips through its language's FFI
-  const Tuning tn = snapshot();
-  const float* g = dOut;
-  const float* terms[kChainMaxSteps + 1];
-  int nterms = 0;
-  for (int m = M - 1; m >= 0; --m) {
-    if (use_residual) terms[nterms++] = g;
-    float* dx = (m == 0 && !use_residual) ? dV0 : dX_steps[m];
-    if (int rc = bwd_impl<float>(tn, g, W_steps[m], m == 0 ? V0 : X_steps[m], dW_steps[m], dx, B, N, L, C, N * C, offsets, stream))
-      return rc;
-    g = dx;
-  }
-  if (use_residual) {
-    terms[nterms++] = g;  // ((g_M + g_{M-1}) + ... + g_1) + g_0
-    return psf_sum_tensors_f32(terms, nterms, B * N * C, dV0, stream);
-  }
-  return PSF_OK;
+  return chain_bwd_impl<float>(dOut, W_steps, V0, X_steps, dW_steps, dV0, dX_steps, M, use_residual, B, N, L, C, offsets, stream);
 }
 
-// The bf16 backward chain in one library call: always the M per-step launches of psf_chord_spmm_bwd_bf16 (the fused step where
-// it applies), the gradient handed from dX_steps[m] to the next step, and one psf_sum_tensors_bf16 pass for the residual —
-// ((g_M + g_{M-1}) + ... + g_1) + g_0 in f32, rounded once: what chord.py's loop does, without M trips through the caller's FFI.
-// There is no one-launch bf16 backward kernel behind it.
 int psf_chord_chain_bwd_bf16(const uint16_t* dOut, const uint16_t* const* W_steps, const uint16_t* V0, const uint16_t* const* X_steps,
                              uint16_t* const* dW_steps, uint16_t* dV0, uint16_t* const* dX_steps, int32_t M, int32_t use_residual,
                              int64_t B, int64_t N, int32_t L, int64_t C, const int64_t* offsets, void* stream) {
-  if (M < 1) return fail(PSF_E_SHAPE, "M must be >= 1");
-  if (!dOut || !W_steps || !V0 || !X_steps || !dW_steps || !dV0) return fail(PSF_E_NULL, "a required pointer is NULL");
-  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
-  if (!g_chain_bwd_fused.load()) return PSF_E_UNSUPPORTED;  // (knob off: the caller runs the steps itself)
-  // the per-step path needs the M gradient buffers and, with the residual, psf_sum_tensors_bf16's limits
-  if (!dX_steps || (use_residual && (M + 1 > 32 || (B * N * C) % 8 != 0))) return PSF_E_UNSUPPORTED;
-  if (B == 0) return PSF_OK;
-  for (int m = 0; m < M; ++m) {
-    const uint16_t* x = m == 0 ? V0 : X_steps[m];
-    if (!W_steps[m] || !x || !dW_steps[m]) return fail(PSF_E_NULL, "step %d: NULL pointer", m);
-    if (dW_steps[m] == W_steps[m]) return fail(PSF_E_ALIAS, "step %d: dW aliases W", m);
-    if (!dX_steps[m]) return fail(PSF_E_NULL, "step %d: dX_steps[m] is NULL", m);
-  }
-  const Tuning tn = snapshot();
-  const uint16_t* g = dOut;
-  const uint16_t* terms[33];
-  int nterms = 0;
-  for (int m = M - 1; m >= 0; --m) {
-    if (use_residual) terms[nterms++] = g;
-    uint16_t* dx = (m == 0 && !use_residual) ? dV0 : dX_steps[m];
-    if (int rc = bwd_impl<__bf16>(tn, reinterpret_cast<const __bf16*>(g), reinterpret_cast<const __bf16*>(W_steps[m]),
-                                  reinterpret_cast<const __bf16*>(m == 0 ? V0 : X_steps[m]), reinterpret_cast<__bf16*>(dW_steps[m]),
-                                  reinterpret_cast<__bf16*>(dx), B, N, L, C, N * C, offsets, stream))
-      return rc;
-    g = dx;
-  }
-  if (use_residual) {
-    terms[nterms++] = g;
-    return psf_sum_tensors_bf16(terms, nterms, B * N * C, dV0, stream);
-  }
-  return PSF_OK;
+  using P = const __bf16*;
+  return chain_bwd_impl<__bf16>(reinterpret_cast<P>(dOut), reinterpret_cast<const P*>(W_steps), reinterpret_cast<P>(V0),
+                                reinterpret_cast<const P*>(X_steps), reinterpret_cast<__bf16* const*>(dW_steps),
+                                reinterpret_cast<__bf16*>(dV0), reinterpret_cast<__bf16* const*>(dX_steps), M, use_residual, B, N, L,
+                                C, offsets, stream);
 }
 
 int64_t psf_mixer_fwd_workspace(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
@@ -1396,13 +1220,8 @@ int psf_mixer_fwd_in_f32(const psf_mixer_input* in, int64_t B, int64_t N, int32_
     la.images = reinterpret_cast<const unsigned char*>(workspace);
     for (int k = 0; k <= M + 1; ++k) la.first_unit[k] = first_unit[k];
     la.V0 = V0;
-    la.store_mask = 0;
     for (int m = 0; m < kMixerLdsMaxSteps; ++m) la.out[m] = m < M ? out_steps[m] : nullptr;
-    for (int m = 0; m < M; ++m) {  // a buffer that a later step overwrites (two-buffer inference) is not stored at all
-      bool later = false;
-      for (int q = m + 1; q < M; ++q) later = later || out_steps[q] == out_steps[m];
-      if (!later) la.store_mask |= 1u << m;
-    }
+    la.store_mask = (uint32_t)chain_store_mask(out_steps, M);  // a buffer that a later step overwrites (two-buffer inference) is not stored at all
     la.M = M, la.N = (int32_t)N, la.C = (int32_t)C, la.E = E, la.L = L, la.CG = (int32_t)(C / 4), la.WS = mp.lds.WS;
     la.TT = (int32_t)(N / 32), la.nu_max = mp.lds.nu_max;
     e = launch_mixer_lds(mp.lds, use_residual != 0, la, offs, (int)B, s);
@@ -1413,9 +1232,7 @@ int psf_mixer_fwd_in_f32(const psf_mixer_input* in, int64_t B, int64_t N, int32_
     return fail(PSF_E_TUNING, "psf_mixer_fwd: mixer_lds=0 but only the LDS-resident kernel covers N=%lld C=%lld", (long long)N, (long long)C);
   // the tile geometry of every launch below
   WinPick pk;
-  pk.tgs = mp.tgs, pk.rows = mlp_step_rows(mp.tgs), pk.nt = 256, pk.TR = mp.TR, pk.KN = mp.KN;
-  pk.tiles_full = (int)(N / mp.TR);
-  pk.ragged = (N % mp.TR) != 0;
+  set_pick(&pk, mp.tgs, mlp_step_rows(mp.tgs), 256, mp.TR, mp.KN, N);
   const int TG = 1 << mp.tgs;
   // The step kernel's full-tile instance takes every row block as TR-aligned (scalar block addresses, fwd_mlp_step.h): N and
   // every far offset multiples of TR, rows of exactly 4 TG channels, a batch element under 2^31 bytes; anything else runs the
@@ -1436,7 +1253,7 @@ int psf_mixer_fwd_in_f32(const psf_mixer_input* in, int64_t B, int64_t N, int32_
     fa.stream = s;
     const bool edge_all = pk.ragged && pk.all_edge;  // the g kernel needs its predicate only for rows >= N
     const int rc = window_launches(tn, pk, edge_all, B, N, L, C, N * C, false, &fa.gm, &fa.edge,
-                                   [&] { return launch_g(mp.tgs, fa); }, "chord_mixer_g launch");
+                                   [&] { return with_tgs<0, kMlpStepTgsMax>(mp.tgs, [&](auto t) { return launch_mixer_g<t()>(fa); }); }, "chord_mixer_g launch");
     if (rc) return rc;
   }
   for (int m = 0; m < M; ++m) {  // (3) the M steps
@@ -1454,7 +1271,7 @@ int psf_mixer_fwd_in_f32(const psf_mixer_input* in, int64_t B, int64_t N, int32_
     fa.stream = s;
     tn.walk_backwards = (m & 1) != 0;  // zigzag, as chain_impl
     const int rc = window_launches(tn, pk, pk.all_edge, B, N, L, C, N * C, false, &fa.gm, &fa.edge,
-                                   [&] { return launch_mlp_step(mp.tgs, L, fa); }, "chord_fwd_mlp launch");
+                                   [&] { return with_tgs<0, kMlpStepTgsMax>(mp.tgs, [&](auto t) { return launch_fwd_mlp<t()>(L, fa); }); }, "chord_fwd_mlp launch");
     if (rc) return rc;
   }
   return PSF_OK;
@@ -1488,81 +1305,49 @@ int psf_get_tuning(const char* key) {
   return fail(PSF_E_TUNING, "unknown tuning key '%s'", key);
 }
 
+// psf_describe_*: the plan of a step or chain as the launch makes it, operands taken as 16-byte aligned (nullptr) and a
+// full-batch V, formatted instead of executed.
 int psf_describe_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_bytes, char* buf, int32_t cap) {
-  if (!buf || cap < 1) return fail(PSF_E_NULL, "buf is NULL");
-  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
-  if (elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return fail(PSF_E_SHAPE, "elem_bytes must be 2 (bf16), 4 or 8");
+  if (int rc = describe_args(B, N, L, C, elem_bytes, true, buf, cap)) return rc;
   Offsets offs;
   make_offsets(N, L, nullptr, &offs);
-  const int vecw = 16 / elem_bytes;
-  const bool vec_ok = C % vecw == 0;
-  WinPick pk;
-  const Tuning tn = snapshot();
-  const int variant = tn.fwd_variant;
-  if (variant != 1 && elem_bytes == 2 && pick_window_bf16(tn, nullptr, B, N, L, C, offs, vec_ok, &pk)) {
-    snprintf(buf, cap, "chord_fwd_win_k<bf16,L=%d,TG=%d,R=%d,NT=%d> TR=%d near=%d far=%d tiles=%s", (int)L,
-             1 << pk.tgs, pk.rows, pk.nt, pk.TR, pk.KN, (int)L - pk.KN,
-             pk.all_edge ? "edge" : (pk.ragged ? "full+ragged" : (pk.aligned ? "full, aligned (scalar block addresses)" : "full")));
-  } else if (variant != 1 && elem_bytes == 4 && pick_window(tn, nullptr, B, N, L, C, offs, vec_ok, &pk, 2, true, 0, true)) {
-    snprintf(buf, cap, "chord_fwd_win_k<f32,L=%d,TG=%d,R=%d,NT=%d> TR=%d near=%d far=%d tiles=%s", (int)L,
-             1 << pk.tgs, pk.rows, pk.nt, pk.TR, pk.KN, (int)L - pk.KN,
-             pk.all_edge ? "edge" : (pk.ragged ? "full+ragged" : (pk.aligned ? "full, aligned (scalar block addresses)" : "full")));
+  const Elem& el = elem_of(elem_bytes);
+  const FwdPlan p = plan_fwd(el, snapshot(), nullptr, nullptr, nullptr, nullptr, B, N, L, C, offs);
+  // (p.refused, fwd_variant = 2 where the window kernel does not apply: a launch fails with PSF_E_TUNING, this entry has
+  // always named the generic kernel. Both kept as they were.)
+  if (p.window) {
+    snprintf(buf, cap, "chord_fwd_win_k<%s,L=%d,TG=%d,R=%d,NT=%d> TR=%d near=%d far=%d tiles=%s", el.name, (int)L, 1 << p.pk.tgs,
+             p.pk.rows, p.pk.nt, p.pk.TR, p.pk.KN, (int)L - p.pk.KN,
+             p.pk.all_edge ? "edge" : (p.pk.ragged ? "full+ragged" : (p.pk.aligned ? "full, aligned (scalar block addresses)" : "full")));
   } else {
-    snprintf(buf, cap, "chord_fwd_generic_k<%s,VEC=%d>", elem_bytes == 2 ? "bf16" : elem_bytes == 4 ? "f32" : "f64", vec_ok ? vecw : 1);
+    snprintf(buf, cap, "chord_fwd_generic_k<%s,VEC=%d>", el.name, p.vec);
   }
   return PSF_OK;
 }
 
-// The kernel(s) of one backward step that wants both gradients, operands taken as 16-byte aligned, a full-batch V: the picks
-// of bwd_impl in bwd_impl's order.
+// The kernel(s) of one backward step that wants both gradients.
 int psf_describe_bwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_bytes, char* buf, int32_t cap) {
-  if (!buf || cap < 1) return fail(PSF_E_NULL, "buf is NULL");
-  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
-  if (elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return fail(PSF_E_SHAPE, "elem_bytes must be 2 (bf16), 4 or 8");
+  if (int rc = describe_args(B, N, L, C, elem_bytes, true, buf, cap)) return rc;
   Offsets offs;
   make_offsets(N, L, nullptr, &offs);
-  const int vecw = 16 / elem_bytes;
-  const bool vec_ok = C % vecw == 0;
-  const char* ty = elem_bytes == 2 ? "bf16" : elem_bytes == 4 ? "f32" : "f64";
-  const Tuning tn = snapshot();
-  const bool win = tn.bwd_variant != 1 && B >= 1;
-  WinPick pk;
-  if (win && elem_bytes == 2 && pick_fused_step_bf16(tn, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, L, C, N * C, offs, &pk)) {
-    snprintf(buf, cap, "chord_bwd_fused_k<bf16,L=%d,TG=%d,NT=%d> TR=%d near=%d far=%d fronts=%d", (int)L, 1 << pk.tgs, pk.nt, pk.TR,
-             pk.KN, (int)L - pk.KN, 1 << fused_fronts_shift_bf16(tn, N, pk.tiles_full));
-    return PSF_OK;
+  const Elem& el = elem_of(elem_bytes);
+  const BwdPlan p = plan_bwd(el, snapshot(), nullptr, nullptr, nullptr, nullptr, nullptr, true, true, B, N, L, C, N * C, offs);
+  // (p.refused, dw_variant = 2 where the chunk-looping kernel does not apply: a launch fails with PSF_E_TUNING, this entry
+  // has always named the dW kernel the automatic route takes next. Both kept as they were.)
+  if (p.fused == Fused::kAligned) {
+    snprintf(buf, cap, "chord_bwd_fused_k<%s,L=%d,TG=%d,NT=%d> TR=%d near=%d far=%d fronts=%d", el.name, (int)L, 1 << p.fpk.tgs, p.fpk.nt,
+             p.fpk.TR, p.fpk.KN, (int)L - p.fpk.KN, 1 << p.ileave);
+  } else if (p.fused == Fused::kEdge) {
+    snprintf(buf, cap, "chord_bwd_fused_edge_k<%s,L=%d,TG=%d,NT=%d> TR=%d near=%d far=%d", el.name, (int)L, 1 << p.fpk.tgs, p.fpk.nt,
+             p.fpk.TR, p.fpk.KN, (int)L - p.fpk.KN);
+  } else {
+    char dw[112], dv[112];
+    if (p.dw == Route::kGeneric) snprintf(dw, sizeof(dw), "chord_dw_generic_k<%s,VEC=%d>", el.name, p.dw_vec);
+    else print_win(dw, sizeof(dw), p.dw == Route::kChunk ? "chord_dw_chunk_k" : "chord_dw_win_k", el, L, p.dwpk);
+    if (p.dv == Route::kGeneric) snprintf(dv, sizeof(dv), "chord_dv_generic_k<%s,VEC=%d>", el.name, p.dv_vec);
+    else print_win(dv, sizeof(dv), "chord_dv_win_k", el, L, p.dvpk);
+    snprintf(buf, cap, "%s + %s", dw, dv);
   }
-  if (win && elem_bytes == 4 && pick_fused_step(tn, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, L, C, N * C, offs, &pk)) {
-    const int fronts = tn.bwd_fronts ? tn.bwd_fronts : (N >= 8192 ? 2 : 1);
-    int sh = 0;
-    while ((2 << sh) <= fronts) ++sh;
-    if (!(sh > 0 && pk.tiles_full % (1 << sh) == 0)) sh = 0;
-    snprintf(buf, cap, "chord_bwd_fused_k<f32,L=%d,TG=%d,NT=%d> TR=%d near=%d far=%d fronts=%d", (int)L, 1 << pk.tgs, pk.nt, pk.TR,
-             pk.KN, (int)L - pk.KN, 1 << sh);
-    return PSF_OK;
-  }
-  if (win && elem_bytes == 4 && pick_fused_edge_step(tn, nullptr, nullptr, nullptr, N, L, C, N * C, offs, &pk)) {
-    snprintf(buf, cap, "chord_bwd_fused_edge_k<f32,L=%d,TG=%d,NT=%d> TR=%d near=%d far=%d", (int)L, 1 << pk.tgs, pk.nt, pk.TR, pk.KN,
-             (int)L - pk.KN);
-    return PSF_OK;
-  }
-  char dw[112], dv[112];
-  snprintf(dw, sizeof(dw), "chord_dw_generic_k<%s,VEC=%d>", ty, vec_ok ? vecw : 1);
-  snprintf(dv, sizeof(dv), "chord_dv_generic_k<%s,VEC=%d>", ty, vec_ok ? vecw : 1);
-  if (win && elem_bytes == 2) {
-    if (C / 8 <= (1 << kWinTgsMaxBf16) && pick_window_bf16(tn, nullptr, B, N, L, C, offs, vec_ok, &pk, 1))
-      snprintf(dw, sizeof(dw), "chord_dw_win_k<bf16,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
-    if (pick_window_bf16(tn, nullptr, B, N, L, C, offs, vec_ok, &pk, 2))
-      snprintf(dv, sizeof(dv), "chord_dv_win_k<bf16,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
-  } else if (win && elem_bytes == 4) {
-    if (tn.dw_variant != 1 && pick_dw_chunk(tn, nullptr, B, N, L, C, offs, vec_ok, &pk))
-      snprintf(dw, sizeof(dw), "chord_dw_chunk_k<f32,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
-    else if (C / 4 <= (1 << kWinTgsMax) && pick_window(tn, nullptr, B, N, L, C, offs, vec_ok, &pk, 1, false))
-      snprintf(dw, sizeof(dw), "chord_dw_win_k<f32,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
-    if (pick_dv(tn, nullptr, B, N, L, C, offs, vec_ok, &pk))
-      snprintf(dv, sizeof(dv), "chord_dv_win_k<f32,L=%d,TG=%d,R=%d,NT=%d>", (int)L, 1 << pk.tgs, pk.rows, pk.nt);
-  }
-  snprintf(buf, cap, "%s + %s", dw, dv);
   return PSF_OK;
 }
 
@@ -1572,25 +1357,20 @@ int psf_describe_chain_fwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M
 
 int psf_describe_chain_fwd_dtype(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, int32_t elem_bytes, char* buf,
                                  int32_t cap) {
-  if (!buf || cap < 1) return fail(PSF_E_NULL, "buf is NULL");
-  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
-  if (elem_bytes != 2 && elem_bytes != 4) return fail(PSF_E_SHAPE, "elem_bytes must be 2 (bf16) or 4");
-  ChainLdsPlan plan;
-  const Tuning tn = snapshot();
-  const int cf = tn.chain_fused;
-  const char* ty = elem_bytes == 2 ? "bf16" : "f32";
-  // (as an inference chain is run: only the last result kept; bf16 under its own gate, operands taken as aligned)
-  if (cf && M >= 2 && M <= kChainMaxSteps && B >= 1 && plan_chain_lds(N, C, L, M, &plan, tn.chain_cc, B, elem_bytes) &&
-      (elem_bytes == 4 || cf == 2 || chain_bf16_gate(plan, N, C))) {
-    if (plan.big)
-      snprintf(buf, cap, "chord_chain_rows_k<%s,L=%d,G=%d,R=%d> one launch for all %d steps, %d threads x %d rows x %d channels, %d workgroup(s) per sequence",
-               ty, (int)L, plan.cc, plan.rows, (int)M, plan.threads, plan.rows, 16 / elem_bytes * plan.cc, plan.chunks);
-    else
-      snprintf(buf, cap, "chord_chain_lds_k<%s,L=%d,CC=%d,R=%d> one launch for all %d steps, %d threads, %d workgroup(s) per sequence",
-               ty, (int)L, plan.cc, plan.rows, (int)M, plan.threads, plan.chunks);
-    return PSF_OK;
-  }
-  return psf_describe_fwd(B, N, L, C, elem_bytes, buf, cap);
+  if (int rc = describe_args(B, N, L, C, elem_bytes, false, buf, cap)) return rc;
+  const Elem& el = elem_of(elem_bytes);
+  // (as an inference chain is run: only the last result kept; bf16 under its own gate. p.grid_ok, B * chunks workgroups
+  // within the grid limit, is the launch's condition only: this entry has never looked at it. Kept.)
+  const ChainPlan p = plan_chain<float>(el, snapshot(), nullptr, nullptr, nullptr, M, true, B, N, L, C);
+  if (!p.one_launch) return psf_describe_fwd(B, N, L, C, elem_bytes, buf, cap);
+  const ChainLdsPlan& plan = p.lds;
+  if (plan.big)
+    snprintf(buf, cap, "chord_chain_rows_k<%s,L=%d,G=%d,R=%d> one launch for all %d steps, %d threads x %d rows x %d channels, %d workgroup(s) per sequence",
+             el.name, (int)L, plan.cc, plan.rows, (int)M, plan.threads, plan.rows, el.vec * plan.cc, plan.chunks);
+  else
+    snprintf(buf, cap, "chord_chain_lds_k<%s,L=%d,CC=%d,R=%d> one launch for all %d steps, %d threads, %d workgroup(s) per sequence",
+             el.name, (int)L, plan.cc, plan.rows, (int)M, plan.threads, plan.chunks);
+  return PSF_OK;
 }
 
 }  // extern "C"
