@@ -18,78 +18,45 @@
 namespace psf {
 namespace {
 
-template <typename K>
-hipError_t raise_lds_limit(K kern, int bytes, std::atomic<int>& done) {
-  if (bytes > 48 * 1024 && !done.load()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    done.store(1);
-  }
-  return hipSuccess;
+// dV, dW and chunk dW take the same arguments; `seen` is the calling instance's own (allow_dynamic_lds, psf_common.h)
+template <int NT, typename K, typename T>
+hipError_t launch_win(K kern, int lds, std::atomic<int>& seen, const BwdWinArgsT<T>& a) {
+  if (hipError_t e = allow_dynamic_lds(kern, lds, seen); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(NT), lds, a.stream, a.dZ, a.WV, a.out, a.gm, a.offs, a.w_total);
+  return hipGetLastError();
 }
 
 template <typename T, int L, int TGS, int R, int NT, bool EDGE>
 hipError_t launch_dw(const BwdWinArgsT<T>& a) {
-  using Cfg = BwdWinCfg<T, L, TGS, R, NT>;
-  auto kern = chord_dw_win_k<T, L, TGS, R, NT, EDGE>;
-  static std::atomic<int> done{0};
-  if (hipError_t e = raise_lds_limit(kern, Cfg::lds_dw, done); e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(NT), Cfg::lds_dw, a.stream, a.dZ, a.WV, a.out, a.gm, a.offs,
-                     a.w_total);
-  return hipGetLastError();
+  static std::atomic<int> seen{0};
+  return launch_win<NT>(chord_dw_win_k<T, L, TGS, R, NT, EDGE>, BwdWinCfg<T, L, TGS, R, NT>::lds_dw, seen, a);
 }
 
 template <typename T, int L, int TGS, int R, int NT, bool EDGE>
 hipError_t launch_dv(const BwdWinArgsT<T>& a) {
-  using Cfg = BwdWinCfg<T, L, TGS, R, NT>;
-  auto kern = chord_dv_win_k<T, L, TGS, R, NT, EDGE>;
-  static std::atomic<int> done{0};
-  if (hipError_t e = raise_lds_limit(kern, Cfg::lds_dv, done); e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(NT), Cfg::lds_dv, a.stream, a.dZ, a.WV, a.out, a.gm, a.offs,
-                     a.w_total);
-  return hipGetLastError();
+  static std::atomic<int> seen{0};
+  return launch_win<NT>(chord_dv_win_k<T, L, TGS, R, NT, EDGE>, BwdWinCfg<T, L, TGS, R, NT>::lds_dv, seen, a);
 }
 
 template <int L, int TGS, int R, int NT, bool EDGE>
 hipError_t launch_dwc(const BwdWinArgs& a) {
-  using Cfg = DwChunkCfg<L, TGS, R, NT>;
-  auto kern = chord_dw_chunk_k<L, TGS, R, NT, EDGE>;
-  static std::atomic<int> done{0};
-  if (hipError_t e = raise_lds_limit(kern, Cfg::lds_bytes, done); e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(NT), Cfg::lds_bytes, a.stream, a.dZ, a.WV, a.out, a.gm, a.offs,
-                     a.w_total);
-  return hipGetLastError();
+  static std::atomic<int> seen{0};
+  return launch_win<NT>(chord_dw_chunk_k<L, TGS, R, NT, EDGE>, DwChunkCfg<L, TGS, R, NT>::lds_bytes, seen, a);
 }
 
 template <int TGS, int R, int NT>
 hipError_t launch_dwc_L(int L, const BwdWinArgs& a) {
-  switch (L) {
-#define PSF_CASE(LL) \
-  case LL:           \
-    return a.edge ? launch_dwc<LL, TGS, R, NT, true>(a) : launch_dwc<LL, TGS, R, NT, false>(a);
-    PSF_CASE(4) PSF_CASE(5) PSF_CASE(6) PSF_CASE(7) PSF_CASE(8) PSF_CASE(9) PSF_CASE(10) PSF_CASE(11)
-    PSF_CASE(12) PSF_CASE(13) PSF_CASE(14) PSF_CASE(15) PSF_CASE(16) PSF_CASE(17) PSF_CASE(18)
-    PSF_CASE(19) PSF_CASE(20)
-#undef PSF_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return with_int<kDwChunkLmin, kDwChunkLmax>(L, [&](auto l) {
+    return a.edge ? launch_dwc<l(), TGS, R, NT, true>(a) : launch_dwc<l(), TGS, R, NT, false>(a);
+  });
 }
 
 template <int TGS, int R, int NT, bool DW, typename T = float>
 hipError_t launch_L(int L, const BwdWinArgsT<T>& a) {
-  switch (L) {
-#define PSF_CASE(LL)                                                                                                  \
-  case LL:                                                                                                            \
-    if constexpr (DW) return a.edge ? launch_dw<T, LL, TGS, R, NT, true>(a) : launch_dw<T, LL, TGS, R, NT, false>(a); \
-    else return a.edge ? launch_dv<T, LL, TGS, R, NT, true>(a) : launch_dv<T, LL, TGS, R, NT, false>(a);
-    PSF_CASE(4) PSF_CASE(5) PSF_CASE(6) PSF_CASE(7) PSF_CASE(8) PSF_CASE(9) PSF_CASE(10) PSF_CASE(11)
-    PSF_CASE(12) PSF_CASE(13) PSF_CASE(14) PSF_CASE(15) PSF_CASE(16) PSF_CASE(17) PSF_CASE(18)
-    PSF_CASE(19) PSF_CASE(20)
-#undef PSF_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return with_int<kWinLmin, kWinLmax>(L, [&](auto l) {
+    if constexpr (DW) return a.edge ? launch_dw<T, l(), TGS, R, NT, true>(a) : launch_dw<T, l(), TGS, R, NT, false>(a);
+    else return a.edge ? launch_dv<T, l(), TGS, R, NT, true>(a) : launch_dv<T, l(), TGS, R, NT, false>(a);
+  });
 }
 
 }  // namespace
@@ -160,35 +127,22 @@ hipError_t launch_fused(const BwdWinArgs& a) {
   }
 #endif
   auto kern = chord_bwd_fused_k<L, TGS, NT, ABL>;
-  int lds = Cfg::lds_bytes + ((ABL & 256) ? 2 * BwdWinCfg<float, L, TGS, 1, NT>::NF * NT * 16 : 0);
-  if (a.wg_per_cu > 0) {  // occupancy limiter as in the forward launcher (fwd_window_inst.hip)
-    const int floor_bytes = kLdsPerCu / (a.wg_per_cu + 1) + 256;
-    if (floor_bytes > lds && floor_bytes <= 64 * 1024) lds = floor_bytes;
-  }
-  static std::atomic<int> done{0};
-  if (lds > 48 * 1024 && done.load() < lds) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    done.store(lds);
-  }
+  const int own = Cfg::lds_bytes + ((ABL & 256) ? 2 * BwdWinCfg<float, L, TGS, 1, NT>::NF * NT * 16 : 0);
+  const int lds = lds_for_wg_limit(own, a.wg_per_cu);
+  static std::atomic<int> seen{0};
+  if (hipError_t e = allow_dynamic_lds(kern, lds, seen); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(NT), lds, a.stream, a.dZ, a.WV, a.V2, a.out2, a.out,
                      a.gm, a.offs, a.w_total);
   return hipGetLastError();
 }
+template <int TGS>
+hipError_t launch_fused_L(int L, const BwdWinArgs& a) {
+  return with_int<kFusedLmin, kFusedLmax>(L, [&](auto l) { return launch_fused<l(), TGS, 256>(a); });
+}
 }  // namespace
 template <int TGS>
 hipError_t launch_bwd_fused(int L, const BwdWinArgs& a) {
-  switch (L) {
-#define PSF_CASE(LL) \
-  case LL:           \
-    return launch_fused<LL, TGS, 256>(a);
-    PSF_CASE(4) PSF_CASE(5) PSF_CASE(6) PSF_CASE(7) PSF_CASE(8) PSF_CASE(9) PSF_CASE(10) PSF_CASE(11)
-    PSF_CASE(12) PSF_CASE(13) PSF_CASE(14) PSF_CASE(15) PSF_CASE(16) PSF_CASE(17) PSF_CASE(18)
-    PSF_CASE(19) PSF_CASE(20)
-#undef PSF_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return launch_fused_L<TGS>(L, a);  // (a lambda in a function with external linkage would export its instances)
 }
 template hipError_t launch_bwd_fused<PSF_TGS>(int L, const BwdWinArgs& a);
 
@@ -197,26 +151,20 @@ template <int L, int TGS, int NT>
 hipError_t launch_fused_edge(const BwdWinArgs& a) {
   using Cfg = BwdFusedEdgeCfg<L, TGS, NT>;
   auto kern = chord_bwd_fused_edge_k<L, TGS, NT>;
-  static std::atomic<int> done{0};
-  if (hipError_t e = raise_lds_limit(kern, Cfg::lds_bytes, done); e != hipSuccess) return e;
+  static std::atomic<int> seen{0};
+  if (hipError_t e = allow_dynamic_lds(kern, Cfg::lds_bytes, seen); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(NT), Cfg::lds_bytes, a.stream, a.dZ, a.WV, a.V2, a.out2, a.out, a.gm, a.offs,
                      a.w_total);
   return hipGetLastError();
 }
+template <int TGS>
+hipError_t launch_fused_edge_L(int L, const BwdWinArgs& a) {
+  return with_int<kFusedLmin, kFusedLmax>(L, [&](auto l) { return launch_fused_edge<l(), TGS, 256>(a); });
+}
 }  // namespace
 template <int TGS>
 hipError_t launch_bwd_fused_edge(int L, const BwdWinArgs& a) {
-  switch (L) {
-#define PSF_CASE(LL) \
-  case LL:           \
-    return launch_fused_edge<LL, TGS, 256>(a);
-    PSF_CASE(4) PSF_CASE(5) PSF_CASE(6) PSF_CASE(7) PSF_CASE(8) PSF_CASE(9) PSF_CASE(10) PSF_CASE(11)
-    PSF_CASE(12) PSF_CASE(13) PSF_CASE(14) PSF_CASE(15) PSF_CASE(16) PSF_CASE(17) PSF_CASE(18)
-    PSF_CASE(19) PSF_CASE(20)
-#undef PSF_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return launch_fused_edge_L<TGS>(L, a);
 }
 template hipError_t launch_bwd_fused_edge<PSF_TGS>(int L, const BwdWinArgs& a);
 #endif

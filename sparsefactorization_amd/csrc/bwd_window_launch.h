@@ -37,6 +37,7 @@ hipError_t launch_dv_win_bf16(int L, const BwdWinArgsT<__bf16>& a);
 // bf16 fused dV + dW step (bwd_fused_bf16.h, units bwd_fused_bf16_inst.hip): 256 threads x 1 row (tile = 256 >> TGS rows), rows of
 // exactly 8 << TGS channels; arguments as the f32 fused step (WV = W, V2 = V, out = dV, out2 = dW)
 constexpr int kFusedBf16TgsMax = 4;
+constexpr int kFusedLmin = kWinLmin, kFusedLmax = kWinLmax;  // compiled link counts of the fused steps, f32 and bf16
 template <int TGS>
 hipError_t launch_bwd_fused_bf16(int L, const BwdWinArgsT<__bf16>& a);
 // chunk-looping dW (bwd_dw_chunk.h) for rows of >= 32 channels: 8 or 16 lanes per row chunk (TGS 3 / 4), 256 threads,
@@ -44,6 +45,7 @@ hipError_t launch_bwd_fused_bf16(int L, const BwdWinArgsT<__bf16>& a);
 // TG=8 R=1 21.0 (15.3 in one launch) / 20.6; TG=16 R=1 15.2 / 20.7; R=2 25.5 / 24.8; 1024 threads x 1 row 28.2 / 33.5;
 // TG=4 27.6 / 26.3; whole-row kernel 29.0 / 26.1 — short tiles with many workgroups per CU win, so only R = 1 is built.
 constexpr int kDwChunkTgsMin = 3, kDwChunkTgsMax = 4;
+constexpr int kDwChunkLmin = kWinLmin, kDwChunkLmax = kWinLmax;  // compiled link counts
 template <int TGS>
 hipError_t launch_dw_chunk(int L, const BwdWinArgs& a);
 // dV: the forward's (TGS, NT) pairs plus 512 threads x 1 row per thread for narrow rows (TGS <= 3): the same 256-row

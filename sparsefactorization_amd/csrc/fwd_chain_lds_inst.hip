@@ -10,13 +10,9 @@ namespace {
 template <int L, int CC, int R, bool RES, int NTMAX>
 hipError_t launch_one(const ChainArgs& a, const Offsets& offs, int B, int threads, int lds_bytes, hipStream_t s) {
   auto kern = chord_chain_lds_k<L, CC, R, RES, NTMAX>;
-  static std::atomic<int> raised{0};
-  if (lds_bytes > 48 * 1024 && !raised.load()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       kChainLdsMaxBytes);
-    if (e != hipSuccess) return e;
-    raised.store(1);
-  }
+  // the first launch beyond 48 KB allows the family's maximum, so no later one has to raise again
+  static std::atomic<int> seen{0};
+  if (hipError_t e = allow_dynamic_lds(kern, lds_bytes > 48 * 1024 ? kChainLdsMaxBytes : 0, seen); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)(B * a.chunks)), dim3(threads), lds_bytes, s, a, offs);
   return hipGetLastError();
 }
@@ -24,12 +20,9 @@ hipError_t launch_one(const ChainArgs& a, const Offsets& offs, int B, int thread
 template <int L, int G, int R, int CAP, bool RES>
 hipError_t launch_rows(const ChainArgs& a, const Offsets& offs, int B, int threads, int lds_bytes, hipStream_t s) {
   auto kern = chord_chain_rows_k<L, G, R, CAP, RES>;
-  static std::atomic<int> raised{0};
-  if (!raised.load()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G * CAP * 16);
-    if (e != hipSuccess) return e;
-    raised.store(1);
-  }
+  static_assert(2 * G * CAP * 16 > 48 * 1024, "both instances hold more than the default limit: the first launch raises it");
+  static std::atomic<int> seen{0};
+  if (hipError_t e = allow_dynamic_lds(kern, 2 * G * CAP * 16, seen); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)(B * a.chunks)), dim3(threads), lds_bytes, s, a, offs);
   return hipGetLastError();
 }
@@ -51,17 +44,9 @@ hipError_t launch_R(const ChainLdsPlan& p, const ChainArgs& a, const Offsets& of
 
 template <int CC>
 hipError_t launch_L(int L, bool res, const ChainLdsPlan& p, const ChainArgs& a, const Offsets& offs, int B, hipStream_t s) {
-  switch (L) {
-#define PSF_CASE(LL) \
-  case LL:           \
-    return res ? launch_R<LL, CC, true>(p, a, offs, B, s) : launch_R<LL, CC, false>(p, a, offs, B, s);
-    PSF_CASE(2) PSF_CASE(3) PSF_CASE(4) PSF_CASE(5) PSF_CASE(6) PSF_CASE(7) PSF_CASE(8) PSF_CASE(9) PSF_CASE(10)
-    PSF_CASE(11) PSF_CASE(12) PSF_CASE(13) PSF_CASE(14) PSF_CASE(15) PSF_CASE(16) PSF_CASE(17) PSF_CASE(18)
-    PSF_CASE(19) PSF_CASE(20)
-#undef PSF_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return with_int<kChainLdsLmin, kChainLdsLmax>(L, [&](auto l) {
+    return res ? launch_R<l(), CC, true>(p, a, offs, B, s) : launch_R<l(), CC, false>(p, a, offs, B, s);
+  });
 }
 
 }  // namespace

@@ -24,14 +24,8 @@ hipError_t launch_one(const FwdMlpArgs& a) {
     if (floor_bytes > lds) lds = floor_bytes;
   }
   if (lds > kLdsPerCuBytes) return hipErrorInvalidValue;
-  if (lds > 48 * 1024) {
-    static std::atomic<int> done{0};
-    if (done.load() < lds) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return e;
-      done.store(lds);
-    }
-  }
+  static std::atomic<int> seen{0};
+  if (hipError_t e = allow_dynamic_lds(kern, lds, seen); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(256), lds, a.stream, a.in, a.V, a.res, a.out, a.images, a.nu, a.E, a.gm,
                      a.offs, a.ablate);
   return hipGetLastError();
@@ -43,21 +37,16 @@ hipError_t launch_flags(const FwdMlpArgs& a) {
   return a.edge ? launch_one<L, TGS, false, true>(a) : launch_one<L, TGS, false, false>(a);
 }
 
+template <int TGS>
+hipError_t launch_L(int L, const FwdMlpArgs& a) {
+  return with_int<kMlpStepLmin, kMlpStepLmax>(L, [&](auto l) { return launch_flags<l(), TGS>(a); });
+}
+
 }  // namespace
 
 template <int TGS>
 hipError_t launch_fwd_mlp(int L, const FwdMlpArgs& a) {
-  switch (L) {
-#define PSF_CASE(LL) \
-  case LL:           \
-    return launch_flags<LL, TGS>(a);
-    PSF_CASE(4) PSF_CASE(5) PSF_CASE(6) PSF_CASE(7) PSF_CASE(8) PSF_CASE(9) PSF_CASE(10) PSF_CASE(11)
-    PSF_CASE(12) PSF_CASE(13) PSF_CASE(14) PSF_CASE(15) PSF_CASE(16) PSF_CASE(17) PSF_CASE(18)
-    PSF_CASE(19) PSF_CASE(20)
-#undef PSF_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return launch_L<TGS>(L, a);  // (a lambda in a function with external linkage would export its instances)
 }
 
 template hipError_t launch_fwd_mlp<PSF_TGS>(int L, const FwdMlpArgs& a);
@@ -67,7 +56,7 @@ hipError_t launch_mixer_g(const FwdMlpArgs& a) {
   if (a.in.kind != 0) return hipErrorInvalidValue;
   const int lds = a.nu * kImgBytes;
   auto launch = [&](auto kern) {
-    if (lds > 48 * 1024) {
+    if (lds > 48 * 1024) {  // (every call, not once per kernel: kept as it is, allow_dynamic_lds would skip the repeats)
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       if (e != hipSuccess) return e;
     }

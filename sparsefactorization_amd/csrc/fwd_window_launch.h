@@ -11,7 +11,6 @@
 namespace psf {
 
 constexpr int kWinLmin = 4, kWinLmax = 20;  // compiled link counts
-constexpr int kLdsPerCu = 160 * 1024;       // gfx950
 constexpr int kWinTgsMax = 6;               // TG = 1 << TGS <= 64 lanes share a row
 
 // Compiled (TGS, NT) pairs: every TGS at 256 threads, plus the "wide-row" configuration: 8 lanes per row

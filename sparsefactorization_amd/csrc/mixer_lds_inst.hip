@@ -28,14 +28,8 @@ namespace {
 template <bool RES, int KIND>
 hipError_t launch_one(const MixerLdsPlan& p, const MixerLdsArgs& a, const Offsets& offs, int B, hipStream_t s) {
   auto kern = chord_mixer_lds_k<RES, KIND>;
-  if (p.lds_bytes > 48 * 1024) {
-    static std::atomic<int> done{0};
-    if (done.load() < p.lds_bytes) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes);
-      if (e != hipSuccess) return e;
-      done.store(p.lds_bytes);
-    }
-  }
+  static std::atomic<int> seen{0};
+  if (hipError_t e = allow_dynamic_lds(kern, p.lds_bytes, seen); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(p.threads), p.lds_bytes, s, a, offs);
   return hipGetLastError();
 }

@@ -130,19 +130,6 @@ Tuning snapshot() {
   return t;
 }
 
-// The run-time channel-group shift `tgs` as a template argument: f(std::integral_constant<int, TGS>) for LO <= tgs <= HI,
-// hipErrorInvalidValue outside. The ranges at the call sites name compiled instances only (a launcher that no unit
-// compiles would fail the link).
-template <int LO, int HI, typename F>
-hipError_t with_tgs(int tgs, F&& f) {
-  if constexpr (LO > HI) {
-    return hipErrorInvalidValue;
-  } else {
-    if (tgs == LO) return f(std::integral_constant<int, LO>{});
-    return with_tgs<LO + 1, HI>(tgs, f);
-  }
-}
-
 int ceil_log2(int64_t x) {
   int s = 0;
   while (((int64_t)1 << s) < x) ++s;
@@ -269,33 +256,33 @@ int near_links(int TR, int32_t L, const Offsets& offs) {
 // Run-time configuration -> compiled instance, by argument type.
 hipError_t launch_win(const WinPick& pk, int L, const FwdWinArgs& a) {
   if (pk.nt == kWideThreads) return pk.tgs == kWideTgs ? launch_fwd_win<kWideTgs, kWideThreads>(pk.rows, L, a) : hipErrorInvalidValue;
-  return with_tgs<0, kWinTgsMax>(pk.tgs, [&](auto t) { return launch_fwd_win<t(), 256>(pk.rows, L, a); });
+  return with_int<0, kWinTgsMax>(pk.tgs, [&](auto t) { return launch_fwd_win<t(), 256>(pk.rows, L, a); });
 }
 hipError_t launch_win(const WinPick& pk, int L, const FwdWinArgsT<__bf16>& a) {
-  return with_tgs<0, kWinTgsMaxBf16>(pk.tgs, [&](auto t) { return launch_fwd_win_bf16<t()>(pk.rows, L, a); });
+  return with_int<0, kWinTgsMaxBf16>(pk.tgs, [&](auto t) { return launch_fwd_win_bf16<t()>(pk.rows, L, a); });
 }
 hipError_t launch_dv(const WinPick& pk, int L, const BwdWinArgs& a) {
   if (pk.nt == kWideThreads) return pk.tgs == kWideTgs ? launch_dv_win<kWideTgs, kWideThreads>(pk.rows, L, a) : hipErrorInvalidValue;
   if (pk.nt == kDvMidThreads)
-    return with_tgs<0, kDvMidTgsMax>(pk.tgs, [&](auto t) { return launch_dv_win<t(), kDvMidThreads>(pk.rows, L, a); });
-  return with_tgs<0, kWinTgsMax>(pk.tgs, [&](auto t) { return launch_dv_win<t(), 256>(pk.rows, L, a); });
+    return with_int<0, kDvMidTgsMax>(pk.tgs, [&](auto t) { return launch_dv_win<t(), kDvMidThreads>(pk.rows, L, a); });
+  return with_int<0, kWinTgsMax>(pk.tgs, [&](auto t) { return launch_dv_win<t(), 256>(pk.rows, L, a); });
 }
 hipError_t launch_dv(const WinPick& pk, int L, const BwdWinArgsT<__bf16>& a) {
-  return with_tgs<0, kWinTgsMaxBf16>(pk.tgs, [&](auto t) { return launch_dv_win_bf16<t()>(L, a); });
+  return with_int<0, kWinTgsMaxBf16>(pk.tgs, [&](auto t) { return launch_dv_win_bf16<t()>(L, a); });
 }
 hipError_t launch_dw(bool chunk, const WinPick& pk, int L, const BwdWinArgs& a) {
-  if (chunk) return with_tgs<kDwChunkTgsMin, kDwChunkTgsMax>(pk.tgs, [&](auto t) { return launch_dw_chunk<t()>(L, a); });
-  return with_tgs<0, kWinTgsMax>(pk.tgs, [&](auto t) { return launch_dw_win<t()>(pk.rows, L, a); });
+  if (chunk) return with_int<kDwChunkTgsMin, kDwChunkTgsMax>(pk.tgs, [&](auto t) { return launch_dw_chunk<t()>(L, a); });
+  return with_int<0, kWinTgsMax>(pk.tgs, [&](auto t) { return launch_dw_win<t()>(pk.rows, L, a); });
 }
 hipError_t launch_dw(bool, const WinPick& pk, int L, const BwdWinArgsT<__bf16>& a) {
-  return with_tgs<0, kWinTgsMaxBf16>(pk.tgs, [&](auto t) { return launch_dw_win_bf16<t()>(L, a); });
+  return with_int<0, kWinTgsMaxBf16>(pk.tgs, [&](auto t) { return launch_dw_win_bf16<t()>(L, a); });
 }
 hipError_t launch_fused(bool edge, int tgs, int L, const BwdWinArgs& a) {
-  if (edge) return with_tgs<0, kFusedTgsMax>(tgs, [&](auto t) { return launch_bwd_fused_edge<t()>(L, a); });
-  return with_tgs<0, kFusedTgsMax>(tgs, [&](auto t) { return launch_bwd_fused<t()>(L, a); });
+  if (edge) return with_int<0, kFusedTgsMax>(tgs, [&](auto t) { return launch_bwd_fused_edge<t()>(L, a); });
+  return with_int<0, kFusedTgsMax>(tgs, [&](auto t) { return launch_bwd_fused<t()>(L, a); });
 }
 hipError_t launch_fused(bool, int tgs, int L, const BwdWinArgsT<__bf16>& a) {
-  return with_tgs<0, kFusedBf16TgsMax>(tgs, [&](auto t) { return launch_bwd_fused_bf16<t()>(L, a); });
+  return with_int<0, kFusedBf16TgsMax>(tgs, [&](auto t) { return launch_bwd_fused_bf16<t()>(L, a); });
 }
 
 // Row widths the fused backward step takes: exactly 4 << tgs channels with a whole row inside one workgroup. Rounds 3-5: up
@@ -1253,7 +1240,7 @@ int psf_mixer_fwd_in_f32(const psf_mixer_input* in, int64_t B, int64_t N, int32_
     fa.stream = s;
     const bool edge_all = pk.ragged && pk.all_edge;  // the g kernel needs its predicate only for rows >= N
     const int rc = window_launches(tn, pk, edge_all, B, N, L, C, N * C, false, &fa.gm, &fa.edge,
-                                   [&] { return with_tgs<0, kMlpStepTgsMax>(mp.tgs, [&](auto t) { return launch_mixer_g<t()>(fa); }); }, "chord_mixer_g launch");
+                                   [&] { return with_int<0, kMlpStepTgsMax>(mp.tgs, [&](auto t) { return launch_mixer_g<t()>(fa); }); }, "chord_mixer_g launch");
     if (rc) return rc;
   }
   for (int m = 0; m < M; ++m) {  // (3) the M steps
@@ -1271,7 +1258,7 @@ int psf_mixer_fwd_in_f32(const psf_mixer_input* in, int64_t B, int64_t N, int32_
     fa.stream = s;
     tn.walk_backwards = (m & 1) != 0;  // zigzag, as chain_impl
     const int rc = window_launches(tn, pk, pk.all_edge, B, N, L, C, N * C, false, &fa.gm, &fa.edge,
-                                   [&] { return with_tgs<0, kMlpStepTgsMax>(mp.tgs, [&](auto t) { return launch_fwd_mlp<t()>(L, fa); }); }, "chord_fwd_mlp launch");
+                                   [&] { return with_int<0, kMlpStepTgsMax>(mp.tgs, [&](auto t) { return launch_fwd_mlp<t()>(L, fa); }); }, "chord_fwd_mlp launch");
     if (rc) return rc;
   }
   return PSF_OK;

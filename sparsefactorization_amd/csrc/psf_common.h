@@ -6,6 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <type_traits>
+
 #include "../../include/psf_chord.h"
 
 namespace psf {
@@ -234,5 +237,49 @@ constexpr int ilog2_floor(int x) { return x <= 1 ? 0 : 1 + ilog2_floor(x >> 1); 
 constexpr int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imin_rt(int a, int b) { return a < b ? a : b; }
 constexpr int imax(int a, int b) { return a > b ? a : b; }
+
+// ---- host side: what the launchers of the *_inst.hip units and the dispatcher share ----
+
+// A run-time integer as a template argument: f(std::integral_constant<int, V>) for LO <= v <= HI, hipErrorInvalidValue
+// outside. f receives the very V that v compared equal to, so a value cannot reach another value's instance. The ranges at
+// the call sites name compiled instances only (a launcher that no unit compiles would fail the link).
+template <int LO, int HI, typename F>
+hipError_t with_int(int v, F&& f) {
+  if constexpr (LO > HI) {
+    return hipErrorInvalidValue;
+  } else {
+    if (v == LO) return f(std::integral_constant<int, LO>{});
+    return with_int<LO + 1, HI>(v, f);
+  }
+}
+
+constexpr int kLdsPerCu = 160 * 1024;  // gfx950
+
+// Occupancy limiter (wg_per_cu of the forward and the fused backward launchers): the LDS bytes to request for an instance
+// that needs own_lds_bytes. A CU takes floor(160 KB / LDS per workgroup) workgroups, so asking for just over
+// 160 KB / (n + 1) caps it at n. (cfg2: 3 per CU is 2-3 % faster than the 4 the registers allow — fewer windows competing
+// for the XCD's L2; 2 per CU is 10 % slower. DESIGN.md §4.1.)
+inline int lds_for_wg_limit(int own_lds_bytes, int wg_per_cu) {
+  if (wg_per_cu > 0) {
+    const int floor_bytes = kLdsPerCu / (wg_per_cu + 1) + 256;
+    if (floor_bytes > own_lds_bytes && floor_bytes <= 64 * 1024) return floor_bytes;
+  }
+  return own_lds_bytes;
+}
+
+// A kernel must be allowed more than 48 KB of dynamic LDS before a launch asks for it. `seen` is the launcher's
+// function-local static, one per kernel instance: the largest size allowed so far, so the attribute is set only when a
+// launch needs more than every launch before it. A launcher whose size is a constant of the instance gets here once; one
+// whose size varies (occupancy limiter, sequence length) either follows its high-water mark or passes the maximum of its
+// family, which makes the first raise the only one.
+template <typename K>
+hipError_t allow_dynamic_lds(K kern, int bytes_needed, std::atomic<int>& seen) {
+  if (bytes_needed > 48 * 1024 && seen.load() < bytes_needed) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes_needed);
+    if (e != hipSuccess) return e;
+    seen.store(bytes_needed);
+  }
+  return hipSuccess;
+}
 
 }  // namespace psf
