@@ -486,72 +486,29 @@ int psf_stream_mix_bwd_f32(const float* w, const float* v, const float* z, float
                            void* stream);
 
 /*
- * Process-wide tuning knobs (benchmark / test use; defaults are the shipped configuration).
- *   key "fwd_variant": 0 = auto, 1 = generic direct-gather kernel, 2 = LDS-window kernel
- *   key "bwd_variant": 0 = auto (LDS-window dV / dW kernels where they apply), 1 = generic kernels
- *   key "fwd_split"  : window kernels (forward, dV, dW) on shapes with a ragged last tile per sequence: 1 = by size
- *                      (default: one launch of the general (edge) instance below ~300 MB of algorithmic bytes, where the
- *                      ~2.7 us of a second launch outweigh predicating every tile; above that as 2); 2 = full tiles on
- *                      the predicate-free instance + the ragged tiles in a second launch; 0 = every tile on the edge
- *                      instance
- *   key "dw_variant" : dW: 0 = auto (chunk-looping kernel for rows of >= 32 channels whose channel groups split into
- *                      chunks of 8, else the whole-row window kernel), 1 = whole-row window kernel, 2 = chunk-looping
- *                      kernel or PSF_E_TUNING where it does not apply
- *   key "dw_tgs"     : chunk-looping dW, lanes per row chunk: 0 = auto (8; 16 when that spares a ragged tile), 4 = 8, 5 = 16
- *   key "dv_threads" : dV window kernel: 0 = auto (512 threads x 1 row for C <= 8, else 256 threads x 2 rows), 1 = 256 threads
- *   key "bwd_fused"  : a backward step that wants both dW and dV: 1 (default) = ONE fused kernel for rows of C = 4, 8, 16, 32 or
- *                      64 channels (128 up to N = 4096) and sequences of at least two tiles — the dZ window staged once serves both gradients:
- *                      the aligned instance (N and the far offsets multiples of the tile, 16-byte-aligned chunk-clean
- *                      buffers: row-block addresses on the scalar unit) or else the general one (any N — N = 2^k + 1 with a
- *                      CLS token —, any far offsets, W / dW at any alignment); 2 = the aligned instance or the two kernels;
- *                      0 = always the two kernels
- *   key "fwd_wide"   : rows of >= 64 channels: 0 = automatic (default): the forward step takes 32-channel chunks on
- *                      1024-thread workgroups (256-row tiles) for rows of 64..256 channels and N <= 4096, one workgroup per
- *                      whole row otherwise; the backward kernels one workgroup per whole row; 1 = the 1024-thread chunks
- *                      wherever they fit (forward and dV); 2 = 32-channel chunks on 256-thread workgroups; 4 (and 3, whose
- *                      512-thread instance for rows of 32 channels was removed in round 5) = one workgroup per whole row
- *                      always
- *   key "chain_fused": 1 (default) = psf_chord_chain_fwd_f32 runs short sequences (N <= 2112, or 4160: see "chain_cc"; L <= 20, C % 4 == 0) as ONE
- *                      launch with the sequence resident in LDS: always when at most two step results are kept (inference
- *                      with alternating buffers), and when every step is kept (training) for sequences of at most 65536
- *                      elements (131072 for N <= 1024; 524288 where the eight-channel instance of "chain_cc" runs);
- *                      0 = always M per-step launches; 2 = the single launch wherever it fits. The workgroups of a
- *                      sequence share an XCD (knob "xcd_remap").
- *   key "fwd_wg_limit": LDS-window forward kernel, workgroups per CU: 0 = auto (3 for rows of <= 8 channels on
- *                      launches of >= 4096 tiles, else unlimited), 1 = unlimited, 2..4 = that many
- *   key "chain_zigzag": per-step launches of psf_chord_chain_fwd_*: 1 = every XCD walks its tile range forwards on
- *                      even steps and backwards on odd ones, so a launch starts on the tiles whose inputs the
- *                      previous launch wrote last (default); 0 = always forwards
- *   key "chain_cc"   : fused chain: channel groups (of 4 channels) per workgroup: 0 = automatic (default): two when the rows allow
- *                      (N <= 1056; N <= 2048 on the one-workgroup-per-CU instance when the launch keeps >= 256 workgroups;
- *                      that instance with one group also runs 2113 <= N <= 4160, the LRA text task, under the same
- *                      condition when only the last result is kept), 1 = one and no instance beyond N = 2112, 2 = the
- *                      one-workgroup-per-CU instances wherever they fit
- *   key "mlp_variant": psf_mlp_fwd_f32: 0 = auto (default: the split-bf16 kernel for E <= 32, else the f32-MFMA
- *                      kernel), 1 = f32 MFMA with streamed weights, 2 = f32 MFMA with LDS-resident weights,
- *                      3 = split-bf16 (each f32 operand as three exact bf16 terms, six product terms: f32 accuracy)
- *   key "bwd_fused_wg_limit": fused backward step: 0 = automatic (default): three workgroups per CU on launches of >= 4096
- *                      tiles, as many as fit below (five of 256 threads at C = 8); n = at most n (by requesting more LDS).
- *                      Round-4 kernel, rotating operands: 42.3 (what fits) / 40.9 (three) us at Order B = 40, 12.6 / 13.5 on
- *                      2048 tiles
- *   key "fwd_rows"   : LDS-window forward kernel, rows per thread: 0 = automatic (default): four for rows of 16..64 channels on
- *                      256-thread workgroups from N = 4096 on where the four-row tile divides N (one far link fewer: 2-6 %
- *                      per step), two otherwise; 2 / 4 = that many where compiled
- *   key "bwd_fronts" : fused backward step (full tiles): 0 = automatic (default): from N = 8192 on every XCD walks the tiles of
- *                      a batch element as TWO interleaved fronts half a sequence apart (the rows the longest link joins are
- *                      then in flight together: Order shape 41.1 -> 39.2 us per step); 1 = one front; 2, 4, 8 = that many
- *                      (speed only: results do not depend on the order of workgroups)
- *   key "wide_fuse"  : psf_mlp_wide_fwd_f32: 1 = the second layers of the MLPs with <= 32 outputs run inside the first
- *                      layers' GEMM epilogue when every MLP has 97..128 hidden rows (default), 0 = always the separate kernel
- *   key "mixer_lds"  : psf_mixer_fwd_*: 1 = short sequences take the single-launch LDS-resident mixer (default), 0 = per-step kernels
- *   key "mixer_wg_limit": psf_mixer_fwd_f32's step kernel, workgroups per CU: 0 = as many as fit (default: three), n = at most n
- *   key "mixer_ablate": TIMING EXPERIMENTS ONLY, and only in a library built with -DPSF_MIXER_ABLATE_LAB (ignored otherwise):
- *                      bit 0 no MLP arithmetic, bit 1 no multiply-add chain, bit 2 no far rows, bit 3 no data rows in
- *                      psf_mixer_fwd_f32's step kernel (profiles/mixer_bench.py)
- *   key "bwd_ablate" : TIMING EXPERIMENTS ONLY, and only in a library built with -DPSF_BWD_ABLATE_LAB (ignored otherwise): parts
- *                      of the fused backward step left out (csrc/bwd_fused.h, ABL; profiles/bwd_ablate_bench.py)
- *   key "xcd_remap"  : 1 = keep a batch element's tiles on one XCD group (default), 0 = linear
- * psf_get_tuning returns the value (>= 0) or PSF_E_TUNING.
+ * Process-wide tuning knobs (benchmark / test use; the defaults are the shipped configuration). psf_chord_tuning.h, beside
+ * this header, is the catalogue: every key with its range, its default and what it selects. psf_set_tuning returns PSF_OK, or
+ * PSF_E_TUNING for a key that is not in the catalogue or a value outside the key's range; psf_get_tuning returns the value
+ * (>= 0) or PSF_E_TUNING.
+ * A knob picks the kernel or launch shape that computes a result; out, dV and the chain results are summed in the same
+ * order on every route (f32: the CPU oracle's bits). What a caller can observe besides time:
+ *   "fwd_variant", "dw_variant", "mlp_variant": a value that forces one kernel makes the call return PSF_E_TUNING where that
+ *                      kernel does not apply. "mlp_variant" also moves psf_mlp_fwd_f32 between the f32-MFMA and the
+ *                      split-bf16 arithmetic: equal to f32 accuracy, not bit for bit.
+ *   "bwd_variant", "bwd_fused", "dw_variant", "dw_tgs": f32 dW is specified to 1e-5 relative, not to the bit (its sum over
+ *                      a row's channels is a tree whose shape belongs to the kernel), so moving a backward step to another
+ *                      dW kernel may change dW's last bits; bf16 dW is the same bits on the fused and the two-kernel route.
+ *   "chain_fused"    : in the one launch a step buffer that a later step overwrites is not written at all
+ *                      (psf_chord_chain_fwd_f32 above); 0 keeps the per-step launches, which write every step.
+ *   "chain_bwd_fused": 0 makes psf_chord_chain_bwd_f32 / _bf16 return PSF_E_UNSUPPORTED and
+ *                      psf_chord_chain_bwd_supported return 0: the caller runs the steps itself.
+ *   "mixer_lds"      : 0 takes the single-launch mixer away: psf_mixer_fwd_plan answers 1 (or 0) instead of 2, an input
+ *                      recipe (psf_mixer_fwd_in_f32 with another kind than PSF_MIXER_IN_DATA) returns PSF_E_SHAPE, and a
+ *                      shape that only the single launch covers returns PSF_E_TUNING.
+ * Every other key ("wide_fuse" among them: same arithmetic in the same order) changes time only.
+ * Change notes: the keys "mixer_ablate" and "bwd_ablate" (timing labs, ignored by every product build) are gone and answer
+ * PSF_E_TUNING like any unknown key; the labs are kept as patches (profiles/bwd_fused_ablate_lab.patch,
+ * profiles/mixer_ablate_lab.patch). No entry point changed: PSF_ABI_VERSION stays 2.
  */
 int psf_set_tuning(const char* key, int32_t value);
 int psf_get_tuning(const char* key);

@@ -46,7 +46,8 @@ def main():
     ap.add_argument("--limits", default="0")
     ap.add_argument("--only", default="")
     ap.add_argument("--alt-lib", default="", help="a second build of the library: its mixer is timed as arm `alt` in the same process")
-    ap.add_argument("--ablate", default="", help="comma list of mixer_ablate masks to time as extra arms (results are wrong)")
+    ap.add_argument("--ablate", default="", help="comma list of mixer_ablate masks to time as extra arms (results are wrong); needs the lab build: git apply "
+                    "profiles/mixer_ablate_lab.patch, PSF_MLP_STEP_EXTRA=-DPSF_MIXER_ABLATE_LAB")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     limits = [int(v) for v in args.limits.split(",")]

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """What the fused backward step's time is made of: the cfg2 / Temporal-Order instance of chord_bwd_fused_k with parts left
-out (csrc/bwd_fused.h, ABL; needs a library built with PSF_HIPCC_EXTRA=-DPSF_BWD_ABLATE_LAB), warm operands (one set) and
+out (template parameter ABL, knob "bwd_ablate": no longer in the product kernel; `git apply profiles/bwd_fused_ablate_lab.patch`
+and build with PSF_HIPCC_EXTRA=-DPSF_BWD_ABLATE_LAB), warm operands (one set) and
 cold ones (10 sets, W / V / outputs rotating, dZ fixed: what a training step sees). us per step, median of five readings of
 100 steps, arms interleaved.
     python profiles/bwd_ablate_bench.py [B N L C]"""

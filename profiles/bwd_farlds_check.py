@@ -1,3 +1,4 @@
+# lab build: git apply profiles/bwd_fused_ablate_lab.patch, then build with PSF_HIPCC_EXTRA=-DPSF_BWD_ABLATE_LAB
 import sys, torch
 sys.path.insert(0, "/root/repo")
 import sparsefactorization_amd as sfa

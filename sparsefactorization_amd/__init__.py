@@ -7,12 +7,12 @@ ABI of include/psf_chord.h); this package is the thin PyTorch-ROCm host side tha
 Python surface. Importing the package does not need a GPU; calling an operator does, and needs the built
 library — nothing falls back to the CPU.
 """
-from ._lib import PSFLibraryError, build_info, describe_fwd, get_tuning, set_tuning
+from ._lib import PSFLibraryError, build_info, describe_fwd, get_tuning, set_tuning, tuning
 from .chord import chord_chain, chord_spmm, get_chord_indices_assym, offsets_from_index, spmm
 from .spmul import SparseMultiply, get_offsets
 
 __all__ = [
     "spmm", "chord_spmm", "chord_chain", "get_chord_indices_assym", "offsets_from_index",
-    "SparseMultiply", "get_offsets", "PSFLibraryError", "build_info", "describe_fwd", "set_tuning", "get_tuning",
+    "SparseMultiply", "get_offsets", "PSFLibraryError", "build_info", "describe_fwd", "set_tuning", "get_tuning", "tuning",
 ]
 __version__ = "0.1.0"

@@ -4,6 +4,7 @@ There is no fallback: if the HIP library is missing or cannot be loaded, every o
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -209,6 +210,19 @@ def get_tuning(key: str) -> int:
     if v < 0:
         raise PSFLibraryError(f"psf_get_tuning({key}): {last_error()}")
     return v
+
+
+@contextlib.contextmanager
+def tuning(**kv):
+    """Set tuning knobs for the length of a ``with`` block; the values they had come back on exit, also after an error."""
+    saved = {k: get_tuning(k) for k in kv}
+    try:
+        for k, v in kv.items():
+            set_tuning(k, v)
+        yield
+    finally:
+        for k, v in saved.items():
+            set_tuning(k, v)
 
 
 def describe_fwd(B: int, N: int, L: int, C: int, elem_bytes: int = 4) -> str:

@@ -27,7 +27,7 @@ WIN_TGS = list(range(7))
 
 HEADERS = ["psf_common.h", "fwd_kernels.h", "fwd_window.h", "fwd_window_launch.h", "bwd_kernels.h",
            "bwd_window.h", "bwd_dw_chunk.h", "bwd_window_launch.h", "bwd_fused.h", "bwd_fused_bf16.h", "fwd_chain_lds.h", "fwd_chain_lds_bf16.h", "fwd_chain_lds_launch.h", "bwd_chain_lds.h", "fwd_mlp_step.h", "fwd_mlp_step_launch.h", "mixer_lds.h", "mixer_lds_launch.h", "mlp_x3_image.h", "mlp_fwd_x3.h", "mlp_x3_common.h", "mlp_planes.h", "x3_gemm.h",
-           os.path.join("..", "..", "include", "psf_chord.h")]
+           os.path.join("..", "..", "include", "psf_chord.h"), os.path.join("..", "..", "include", "psf_chord_tuning.h")]
 SOURCES = ["psf_chord.hip", "fwd_window_inst.hip", "bwd_window_inst.hip", "bwd_fused_bf16_inst.hip", "linear_wgrad.hip",
            "fwd_chain_lds_inst.hip", "fwd_chain_lds_bf16_inst.hip", "bwd_chain_lds_inst.hip", "fwd_mlp_step_inst.hip", "mixer_lds_inst.hip", "embed.hip", "flat_head.hip", "sum_tensors.hip", "adam.hip", "mlp_fwd.hip", "mlp_fwd_x3.hip", "mlp_bwd.hip", "mlp_wide.hip", "stream_mix.hip"]
 
@@ -37,13 +37,13 @@ HIPCC_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-ffp-con
 
 
 def csrc_hash() -> str:
-    """SHA-256 over the kernel sources (every file under csrc/ plus include/psf_chord.h, names and contents, sorted).
+    """SHA-256 over the kernel sources (every file under csrc/ plus include/psf_chord.h and psf_chord_tuning.h, names and contents, sorted).
     Identifies the code a profile was collected on: profiles/*_pmc.json records it and bench.py withholds
     ``roofline.traffic`` when it no longer matches (no .git on the GPU box, so a content hash instead of a commit)."""
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip")))
-    files.append(os.path.join(PKG_DIR, "..", "include", "psf_chord.h"))
+    files += [os.path.join(PKG_DIR, "..", "include", h) for h in ("psf_chord.h", "psf_chord_tuning.h")]
     for f in files:
         h.update(os.path.basename(f).encode())
         with open(f, "rb") as fh:

@@ -43,13 +43,7 @@ struct BwdFusedCfg {
 // Wider rows have more far links to hold (8 at C = 32): under that bound the C = 32 instance spilled 22 registers and took
 // 99 us per step where the 512-thread one takes 54 (genome shape, profiles/r03ap_bwd_fused_c32.log), so the bound is for the
 // narrow instances only.
-//
-// ABL (diagnostic builds only, -DPSF_BWD_ABLATE_LAB, tuning knob "bwd_ablate"; 0 in the product): leave parts out to see what
-// the step's time is made of — 1 far dZ / V rows, 2 far W elements, 4 the dZ and V windows, 8 the W tiles, 16 dV's
-// arithmetic, 32 dW's arithmetic, 64 the stores (results are then wrong by construction); variants that stay correct: 128 dW
-// stored non-temporally, 512 dW's dots contracted to FMAs, 256 (round 6) the far dZ / V rows by LDS-DMA into LDS (2 NF NT 16
-// more bytes of LDS: 48 KB at C = 8) instead of 2 NF 16-byte register loads per thread.
-template <int L, int TGS, int NT, int ABL = 0>
+template <int L, int TGS, int NT>
 __global__ void __launch_bounds__(NT, (NT == 256 && TGS <= 1) ? 5 : 2)
 chord_bwd_fused_k(const float* __restrict__ dZ, const float* __restrict__ W, const float* __restrict__ V,
                   float* __restrict__ dW, float* __restrict__ dV, const Geom gm, const Offsets offs, const int64_t w_total) {
@@ -64,8 +58,6 @@ chord_bwd_fused_k(const float* __restrict__ dZ, const float* __restrict__ W, con
   V4* __restrict__ sWV = reinterpret_cast<V4*>(smem + 2 * Cfg::win_bytes);
   const T* __restrict__ sWF = reinterpret_cast<const T*>(sWV);
   T* __restrict__ sOutF = reinterpret_cast<T*>(sWV);  // the dW tile image: written after the last read of the W tiles
-  V4* __restrict__ sFarZ = reinterpret_cast<V4*>(smem + FC::lds_bytes);  // ABL & 256 only: [NF][NT] far dZ rows, then far V rows
-  V4* __restrict__ sFarV = sFarZ + (NF > 0 ? NF : 1) * NT;
 
   int b, tile, chunk;
   decode_block(gm, b, tile, chunk);  // chunks_c == 1
@@ -93,12 +85,10 @@ chord_bwd_fused_k(const float* __restrict__ dZ, const float* __restrict__ W, con
   // chunk index instead of masking lanes — the surplus lanes re-read the tile's last chunk into LDS slots nobody reads.
   // (1) dZ window: slot wr <-> row (q0 - TR + wr) mod N;  V window: slot wr <-> row (q0 + wr) mod N  (one pass per block)
   static_assert(Cfg::win_vecs / NT == 2, "one row per thread: a window is two passes of TR rows");
-  if constexpr (!(ABL & 4)) {
-    stage16g<0>(sbase(Zbb + (uint32_t)prev0 * rowB) + voff, sZ + wave64);
-    stage16g<0>(sbase(Vbb + (uint32_t)q0 * rowB) + voff, sV + wave64);
-    stage16g<0>(sbase(Zbb + (uint32_t)q0 * rowB) + voff, sZ + NT + wave64);
-    stage16g<0>(sbase(Vbb + (uint32_t)next0 * rowB) + voff, sV + NT + wave64);
-  }
+  stage16g<0>(sbase(Zbb + (uint32_t)prev0 * rowB) + voff, sZ + wave64);
+  stage16g<0>(sbase(Vbb + (uint32_t)q0 * rowB) + voff, sV + wave64);
+  stage16g<0>(sbase(Zbb + (uint32_t)q0 * rowB) + voff, sZ + NT + wave64);
+  stage16g<0>(sbase(Vbb + (uint32_t)next0 * rowB) + voff, sV + NT + wave64);
   // (2) far links -> registers
   V4 farZ[NF > 0 ? NF : 1], farV[NF > 0 ? NF : 1];
   T farW[NF > 0 ? NF : 1];
@@ -109,49 +99,33 @@ chord_bwd_fused_k(const float* __restrict__ dZ, const float* __restrict__ W, con
     if (src0[f] < 0) src0[f] += N;
     int dst0 = q0 + offs.v[KN + f];
     if (dst0 >= N) dst0 -= N;
-    if constexpr ((ABL & 256) != 0) {
-      stage16g<0>(sbase(Zbb + (uint32_t)src0[f] * rowB) + voff, sFarZ + f * NT + wave64);
-      stage16g<0>(sbase(Vbb + (uint32_t)dst0 * rowB) + voff, sFarV + f * NT + wave64);
-    } else if constexpr (!(ABL & 1)) {
-      farZ[f] = ldg<T, VEC>(sbase(Zbb + (uint32_t)src0[f] * rowB) + voff);
-      farV[f] = ldg<T, VEC>(sbase(Vbb + (uint32_t)dst0 * rowB) + voff);
-    } else {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) farZ[f].e[i] = T(src0[f]), farV[f].e[i] = T(dst0);
-    }
+    farZ[f] = ldg<T, VEC>(sbase(Zbb + (uint32_t)src0[f] * rowB) + voff);
+    farV[f] = ldg<T, VEC>(sbase(Vbb + (uint32_t)dst0 * rowB) + voff);
   }
   // (3) the two W tiles under the backward window, flat 16-byte chunks. The upper tile's last pass clamps (its surplus lanes
   //     land in the pad); the lower tile's would land on the upper tile's first chunks, so it is lane-masked and comes LAST
   //     of all requests (3c).
   auto w_tile = [&](int row0) { return reinterpret_cast<const char*>(W + ((int64_t)b * N + row0) * L); };
-  if constexpr (!(ABL & 8)) {
-    const char* __restrict__ wp = w_tile(prev0);
-    const char* __restrict__ wc = w_tile(q0);
+  const char* __restrict__ wp = w_tile(prev0);
+  const char* __restrict__ wc = w_tile(q0);
 #pragma unroll
-    for (int n = 0; n < FC::full; ++n) {
-      stage16g<0>(sbase(wp + (size_t)n * NT * 16) + voff, sWV + n * NT + wave64);
-      stage16g<0>(sbase(wc + (size_t)n * NT * 16) + voff, sWV + FC::tile_vecs + n * NT + wave64);
-    }
-    if constexpr (FC::rem > 0) {
-      const uint32_t i = (uint32_t)imin_rt(tid, FC::rem - 1);
-      stage16g<0>(sbase(wc + (size_t)FC::full * NT * 16) + i * 16u, sWV + FC::tile_vecs + FC::full * NT + wave64);
-    }
+  for (int n = 0; n < FC::full; ++n) {
+    stage16g<0>(sbase(wp + (size_t)n * NT * 16) + voff, sWV + n * NT + wave64);
+    stage16g<0>(sbase(wc + (size_t)n * NT * 16) + voff, sWV + FC::tile_vecs + n * NT + wave64);
+  }
+  if constexpr (FC::rem > 0) {
+    const uint32_t i = (uint32_t)imin_rt(tid, FC::rem - 1);
+    stage16g<0>(sbase(wc + (size_t)FC::full * NT * 16) + i * 16u, sWV + FC::tile_vecs + FC::full * NT + wave64);
   }
   // (3b) far-link W elements: element (src0 + pl) of the link's column of row-major W (a contiguous side copy, lane-packed
   //      loads and the far rows through LDS were all measured and dropped: DESIGN.md 4.10)
-  if constexpr (!(ABL & 2)) {
 #pragma unroll
-    for (int f = 0; f < NF; ++f)
-      farW[f] = *reinterpret_cast<const PSF_GLOBAL T*>(sbase(reinterpret_cast<const char*>(Wb + (int64_t)src0[f] * L + (KN + f))) +
-                                                       (uint32_t)pl * (uint32_t)(L * sizeof(T)));
-  } else {
-#pragma unroll
-    for (int f = 0; f < NF; ++f) farW[f] = T(f);
-  }
+  for (int f = 0; f < NF; ++f)
+    farW[f] = *reinterpret_cast<const PSF_GLOBAL T*>(sbase(reinterpret_cast<const char*>(Wb + (int64_t)src0[f] * L + (KN + f))) +
+                                                     (uint32_t)pl * (uint32_t)(L * sizeof(T)));
   // (3c) the lower W tile's partial pass
-  if constexpr (!(ABL & 8) && FC::rem > 0) {
-    if (tid < FC::rem)
-      stage16g<0>(sbase(w_tile(prev0) + (size_t)FC::full * NT * 16) + voff, sWV + FC::full * NT + wave64);
+  if constexpr (FC::rem > 0) {
+    if (tid < FC::rem) stage16g<0>(sbase(w_tile(prev0) + (size_t)FC::full * NT * 16) + voff, sWV + FC::full * NT + wave64);
   }
   __syncthreads();
 
@@ -160,19 +134,15 @@ chord_bwd_fused_k(const float* __restrict__ dZ, const float* __restrict__ W, con
     V4 acc;
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc.e[i] = T(0);
-    if constexpr (!(ABL & 16)) {
 #pragma unroll
-      for (int k = 0; k < KN; ++k) {
-        const int wr = TR + pl - chord_off(k);  // in [0, 2 TR)
-        axpy_rn<T, VEC>(acc, sWF[wr * L + k], sZ[(wr << TGS) + g]);
-      }
+    for (int k = 0; k < KN; ++k) {
+      const int wr = TR + pl - chord_off(k);  // in [0, 2 TR)
+      axpy_rn<T, VEC>(acc, sWF[wr * L + k], sZ[(wr << TGS) + g]);
     }
 #pragma unroll
-    for (int f = 0; f < NF; ++f) axpy_rn<T, VEC>(acc, farW[f], (ABL & 256) ? sFarZ[f * NT + tid] : farZ[f]);
-    if (!(ABL & 64) || acc.e[0] == T(12345.678)) {
-      // dV is a plain store: the next (earlier) step reads it at once (non-temporal measured and dropped: DESIGN.md 4.10)
-      stg<T, VEC>(sbase(reinterpret_cast<char*>(dV + ((int64_t)b * N + q0) * C)) + lane_off(voff), acc);
-    }
+    for (int f = 0; f < NF; ++f) axpy_rn<T, VEC>(acc, farW[f], farZ[f]);
+    // dV is a plain store: the next (earlier) step reads it at once (non-temporal measured and dropped: DESIGN.md 4.10)
+    stg<T, VEC>(sbase(reinterpret_cast<char*>(dV + ((int64_t)b * N + q0) * C)) + lane_off(voff), acc);
   }
   // (5) dW row dots (the tile's dZ rows are the upper half of the dZ window)
   T dots[L];
@@ -181,27 +151,16 @@ chord_bwd_fused_k(const float* __restrict__ dZ, const float* __restrict__ W, con
 #pragma unroll
     for (int k = 0; k < L; ++k) {
       V4 x;
-      if (k < KN) x = (ABL & 32) ? dz : sV[((pl + chord_off(k)) << TGS) + g];
-      else x = (ABL & 256) ? sFarV[(k - KN < NF ? k - KN : 0) * NT + tid] : farV[k - KN < NF ? k - KN : 0];
+      if (k < KN) x = sV[((pl + chord_off(k)) << TGS) + g];
+      else x = farV[k - KN < NF ? k - KN : 0];
       // the lane's four products as two packed multiplies, summed pairwise: (p0 + p2) + (p1 + p3) — four instructions. (Written
       // as a running sum, hipcc paired the sums of two LINKS into packed adds and paid four register moves per pair: eight
       // instructions per link. dW is held to 1e-5, not to the oracle's bits: its sum over a row's lanes is a tree already.)
       using F2 = float __attribute__((ext_vector_type(2)));
-      T part;
-      if constexpr ((ABL & 512) != 0) {
-        part = T(0);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) part = __builtin_fmaf(dz.e[i], x.e[i], part);
-      } else {
-        const F2 pa = F2{dz.e[0], dz.e[1]} * F2{x.e[0], x.e[1]}, pb = F2{dz.e[2], dz.e[3]} * F2{x.e[2], x.e[3]};
-        const F2 ps = pa + pb;
-        part = add_rn(ps.x, ps.y);
-      }
-      dots[k] = row_group_sum<TG>(part);
+      const F2 pa = F2{dz.e[0], dz.e[1]} * F2{x.e[0], x.e[1]}, pb = F2{dz.e[2], dz.e[3]} * F2{x.e[2], x.e[3]};
+      const F2 ps = pa + pb;
+      dots[k] = row_group_sum<TG>(add_rn(ps.x, ps.y));
     }
-  }
-  if constexpr ((ABL & 64) != 0) {
-    if (dots[0] != T(12345.678)) return;
   }
   __syncthreads();  // every thread is done with the W tiles: their first image becomes the dW tile
   if (g == 0) {

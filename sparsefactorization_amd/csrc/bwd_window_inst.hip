@@ -108,26 +108,11 @@ template hipError_t launch_dv_win<PSF_TGS, PSF_NT>(int rows, int L, const BwdWin
 
 #if PSF_NT == 512
 namespace {
-template <int L, int TGS, int NT, int ABL = 0>
+template <int L, int TGS, int NT>
 hipError_t launch_fused(const BwdWinArgs& a) {
   using Cfg = BwdFusedCfg<L, TGS, NT>;
-#ifdef PSF_BWD_ABLATE_LAB  // diagnostic builds: the cfg2 instance with parts left out (bwd_fused.h, ABL)
-  if constexpr (ABL == 0 && L == 15 && TGS == 1 && NT == 256) {
-    switch (a.ablate) {
-#define PSF_ABL(X) \
-  case X:          \
-    return launch_fused<L, TGS, NT, X>(a);
-      PSF_ABL(1) PSF_ABL(2) PSF_ABL(3) PSF_ABL(4) PSF_ABL(8) PSF_ABL(12) PSF_ABL(15) PSF_ABL(16) PSF_ABL(32) PSF_ABL(48)
-      PSF_ABL(63) PSF_ABL(64) PSF_ABL(79) PSF_ABL(112) PSF_ABL(115) PSF_ABL(124) PSF_ABL(128) PSF_ABL(512) PSF_ABL(640)
-      PSF_ABL(256) PSF_ABL(258) PSF_ABL(320) PSF_ABL(368)
-#undef PSF_ABL
-      default:
-        break;
-    }
-  }
-#endif
-  auto kern = chord_bwd_fused_k<L, TGS, NT, ABL>;
-  const int own = Cfg::lds_bytes + ((ABL & 256) ? 2 * BwdWinCfg<float, L, TGS, 1, NT>::NF * NT * 16 : 0);
+  auto kern = chord_bwd_fused_k<L, TGS, NT>;
+  const int own = Cfg::lds_bytes;
   const int lds = lds_for_wg_limit(own, a.wg_per_cu);
   static std::atomic<int> seen{0};
   if (hipError_t e = allow_dynamic_lds(kern, lds, seen); e != hipSuccess) return e;

@@ -59,11 +59,10 @@ struct MlpStepCfg {
 // Temporal-Order networks (SyntheticExperiments/psf.py:153-154: init_linear) or the token embedding plus positional row
 // (psf.py:151-152,157-162; LRA/psf.py:204-209) — so that `data` does not have to exist in memory either.
 template <int KIND>  // compiled per recipe: with the three of them behind a run-time branch in one kernel the step took 7 % longer
-__device__ __forceinline__ void data_row8(const MixerIn& in, const float* sAff, int b, int row, int N, int E, int e0, bool skip,
+__device__ __forceinline__ void data_row8(const MixerIn& in, const float* sAff, int b, int row, int N, int E, int e0,
                                           float (&v)[8]) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) v[i] = 0.f;
-  if (skip) return;
   constexpr int kind = KIND;  // (profiles/r04k_mixer_kind_ab.log: 884 us with in.kind read at run time, 826 compiled in)
   if constexpr (kind == 0) {
     const float* __restrict__ xr = reinterpret_cast<const float*>(in.src) + ((int64_t)b * N + row) * E;
@@ -189,15 +188,9 @@ template <int L, int TGS, bool RES, bool EDGE>
 __global__ void __launch_bounds__(256, 3)
 chord_fwd_mlp_k(const MixerIn in, const float* __restrict__ V, const float* __restrict__ res,
                 float* __restrict__ out, const unsigned char* __restrict__ images, const int nu, const int E, const Geom gm,
-                const Offsets offs, const int ablate_arg) {
+                const Offsets offs) {
   using namespace psf_x3;
   using Cfg = MlpStepCfg<L, TGS>;
-#ifdef PSF_MIXER_ABLATE_LAB  // timing experiments (tuning key "mixer_ablate"): compiled out of the product, where the key is ignored
-  const int ablate = ablate_arg;
-#else
-  constexpr int ablate = 0;
-  (void)ablate_arg;
-#endif
   constexpr int NT = Cfg::NT, R = Cfg::R, TG = Cfg::TG, RS = Cfg::RS, TR = Cfg::TR, KN = Cfg::KN, NF = Cfg::NF;
   constexpr int WS = Cfg::WS, TT = Cfg::TT, G = Cfg::G, TPW = Cfg::TPW;
   using V4 = Vec<float, 4>;
@@ -235,7 +228,7 @@ chord_fwd_mlp_k(const MixerIn in, const float* __restrict__ V, const float* __re
     if constexpr (KIND == 0 && !EDGE) {
       // rows of 32 features in a full tile: one scalar block address per token tile plus one lane offset (the row c, the
       // lane's 8-feature group), four unconditional 16-byte loads (other widths keep the predicated form below)
-      if (E == 32 && !(ablate & 8)) {
+      if (E == 32) {
         const PSF_GLOBAL char* blk = sbase(reinterpret_cast<const char*>(in.src) + ((int64_t)b * N + p0 + 32 * t) * (32 * 4));
         const uint32_t xo = (uint32_t)c * 128u + (uint32_t)half * 32u;
 #pragma unroll
@@ -248,7 +241,7 @@ chord_fwd_mlp_k(const MixerIn in, const float* __restrict__ V, const float* __re
       }
     }
 #pragma unroll
-    for (int s = 0; s < 2; ++s) data_row8<KIND>(in, sAff, b, row, N, E, 16 * s + 8 * half, (ablate & 8) != 0, xv[tp][s]);
+    for (int s = 0; s < 2; ++s) data_row8<KIND>(in, sAff, b, row, N, E, 16 * s + 8 * half, xv[tp][s]);
   }
 
   // ---- (0b) unit images of this step's MLP and the V window [p0, p0 + 2 TR) mod N, by LDS-DMA ----
@@ -281,7 +274,6 @@ chord_fwd_mlp_k(const MixerIn in, const float* __restrict__ V, const float* __re
     for (int f = 0; f < NF; ++f) {
       int s0 = p0 + offs.v[KN + f];
       if (s0 >= N) s0 -= N;
-      if (ablate & 4) s0 = p0;  // timing only: the tile's own rows (L2 / window hits) instead of the far ones
       const PSF_GLOBAL char* blk = sbase(Vbb + (uint32_t)s0 * rowB);
 #pragma unroll
       for (int j = 0; j < R; ++j) far[j][f] = ldg<float, 4>(blk + voff[j]);
@@ -306,7 +298,6 @@ chord_fwd_mlp_k(const MixerIn in, const float* __restrict__ V, const float* __re
       for (int f = 0; f < NF; ++f) {
         int src = p + offs.v[KN + f];
         if (src >= N) src -= N;
-        if (ablate & 4) src = p;  // timing only: the row itself (an L2 / window hit) instead of the far row
         far[j][f] = ld<float, 4>(Vb + (int64_t)src * C + (int64_t)cgc * 4);
       }
     }
@@ -324,7 +315,7 @@ chord_fwd_mlp_k(const MixerIn in, const float* __restrict__ V, const float* __re
   f32x16 acc2[TPW];
 #pragma unroll
   for (int tp = 0; tp < TPW; ++tp) {
-    acc2[tp] = mlp_tile(sImg, (ablate & 1) ? u1 : u0, u1, grp == 0, xv[tp], c, half);  // ablate & 1 (timing only): W = bias
+    acc2[tp] = mlp_tile(sImg, u0, u1, grp == 0, xv[tp], c, half);
     if constexpr (G == 1) {  // the finished tile goes to LDS at once (its registers are free for the next tile)
       constexpr int NQ1 = (L + 7) / 8;
       float* dst = sW + (32 * (wv * TPW + tp) + c) * WS;
@@ -416,10 +407,6 @@ chord_fwd_mlp_k(const MixerIn in, const float* __restrict__ V, const float* __re
 #pragma unroll
     for (int k = 0; k < L; ++k) behind_wait(wk[k]);
     __builtin_amdgcn_sched_barrier(0);
-    if (ablate & 2) {  // timing only: operands consumed, no multiply-add chain
-#pragma unroll
-      for (int k = 0; k < KN; ++k) acc[j].e[k & 3] += xs[k].e[k & 3] + wk[k];
-    } else
 #pragma unroll
     for (int k = 0; k < KN; ++k) axpy_rn<float, 4>(acc[j], wk[k], xs[k]);
 #pragma unroll
@@ -493,7 +480,7 @@ chord_mixer_g_k(const MixerIn in, float* __restrict__ out, const unsigned char* 
       }
     }
 #pragma unroll
-    for (int s = 0; s < 2; ++s) data_row8<KIND>(in, sAff, b, rowc, N, E, 16 * s + 8 * half, false, xv[i][s]);
+    for (int s = 0; s < 2; ++s) data_row8<KIND>(in, sAff, b, rowc, N, E, 16 * s + 8 * half, xv[i][s]);
   }
   __syncthreads();
 #pragma unroll

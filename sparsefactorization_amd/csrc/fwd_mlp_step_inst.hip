@@ -27,7 +27,7 @@ hipError_t launch_one(const FwdMlpArgs& a) {
   static std::atomic<int> seen{0};
   if (hipError_t e = allow_dynamic_lds(kern, lds, seen); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(a.gm.nblocks), dim3(256), lds, a.stream, a.in, a.V, a.res, a.out, a.images, a.nu, a.E, a.gm,
-                     a.offs, a.ablate);
+                     a.offs);
   return hipGetLastError();
 }
 

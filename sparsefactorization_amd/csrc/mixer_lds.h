@@ -62,7 +62,7 @@ chord_mixer_lds_k(const MixerLdsArgs a, const Offsets offs) {
     const int t = wv + i * nwaves;
     const int row = 32 * (t < a.TT ? t : 0) + c;
 #pragma unroll
-    for (int s = 0; s < 2; ++s) data_row8<KIND>(a.in, sAff, b, row, N, a.E, 16 * s + 8 * half, false, xv[i][s]);
+    for (int s = 0; s < 2; ++s) data_row8<KIND>(a.in, sAff, b, row, N, a.E, 16 * s + 8 * half, xv[i][s]);
   }
   __syncthreads();  // image of g landed
 

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "../../include/psf_chord_tuning.h"
 #include "bwd_kernels.h"
 #include "bwd_window_launch.h"
 #include "bwd_chain_lds.h"
@@ -47,53 +48,17 @@ int fail_hip(hipError_t e, const char* what) {
   return (int)e;
 }
 
-// Every knob of this unit, once: X(name, lo, hi, default). The list makes the atomic g_<name>, the member of Tuning, its
-// load in snapshot() and the row of g_knobs that psf_set_tuning / psf_get_tuning search by name.
-//   fwd_variant: 0 auto, 1 generic, 2 window
-//   bwd_variant: 0 auto, 1 generic
-//   fwd_split: 1 = full tiles on the predicate-free kernel + the ragged last tiles in a second small launch, except on small
-//     problems (one predicated launch); 2 = always two launches; 0 = always one predicated launch
-//   dv_threads: dV workgroup: 0 = auto (512 threads x 1 row for rows of <= 8 channels), 1 = 256 threads x 2 rows
-//   bwd_fused: 0 = never, 1 = auto, 2 = wherever the fused step kernel applies
-//   dw_variant: dW: 0 = auto (chunk-looping kernel for C >= 32), 1 = whole-row window kernel, 2 = chunk forced
-//   dw_tgs: chunk-looping dW: 0 = auto, 4 = 8 lanes per row chunk, 5 = 16 lanes
-//   chain_fused: 1 = short sequences run the whole chain in one LDS-resident launch
-//   chain_bwd_fused: psf_chord_chain_bwd_f32: 1 = the one-launch kernel where it fits, 0 = never (PSF_E_UNSUPPORTED)
-//   chain_cc: fused chain: 0 = auto channel groups per workgroup, 1 = one, 2 = two wherever it fits
-//   fwd_wide: Rows of >= 64 channels: 0 = one workgroup spans the whole row (default); 1 = 32-channel chunks on 1024-thread
-//     workgroups (256-row tiles, far links 6 -> 2 at L=12); 2 = 32-channel chunks on 256-thread workgroups.
-//     r01 sweep (us/launch): cfg3 C=128: 18.9 / 23.2 / 21.8; attention map C=1024: 19.2 / 20.5 / 20.9; C=64: 10.2 / 9.4 /
-//     10.0 — contiguous whole-row bursts beat fewer far links, so 0 stays the default.
-//   fwd_wg_limit: Forward window kernel, workgroups per CU: 0 = auto (3 for narrow rows on large launches), 1 = no limit,
-//     2..4 = cap
-//   bwd_fused_wg_limit: fused backward step: 0 = whatever fits (five of 256 threads at C = 8), n = at most n
-//   chain_zigzag: Per-step launches of a chain: 1 = alternate the direction in which each XCD walks its tile range
-//   bwd_fronts: fused backward step: interleaved fronts per batch element, 0 = auto (2 from N = 8192 on), 1, 2, 4, 8
-//   fwd_rows: forward window kernel, rows per thread: 0 = auto, 2, 4 (4: where compiled, fwd_window_launch.h)
-//   bwd_ablate: fused backward step, -DPSF_BWD_ABLATE_LAB builds only (bwd_fused.h: ABL); ignored otherwise
-//   mixer_ablate: timing experiments on that kernel: bit 0 no MLP arithmetic, 1 no multiply-add chain, 2 no far rows, 3 no
-//     data rows
-//   mixer_lds: psf_mixer_fwd_*: 1 = short sequences take the single-launch LDS-resident mixer (mixer_lds.h)
-//   mixer_wg_limit: step kernel that computes its own W (fwd_mlp_step.h): 0 = whatever fits, n = at most n per CU
-#define PSF_KNOBS(X)                                                                                                    \
-  X(fwd_variant, 0, 2, 0) X(bwd_variant, 0, 1, 0) X(xcd_remap, 0, 1, 1) X(fwd_split, 0, 2, 1) X(fwd_wide, 0, 4, 0)      \
-  X(dw_variant, 0, 2, 0) X(dv_threads, 0, 1, 0) X(bwd_fused, 0, 2, 1) X(bwd_fused_wg_limit, 0, 5, 0) X(dw_tgs, 0, 5, 0) \
-  X(fwd_wg_limit, 0, 4, 0) X(chain_zigzag, 0, 1, 1) X(mixer_wg_limit, 0, 4, 0) X(mixer_lds, 0, 1, 1)                    \
-  X(mixer_ablate, 0, 15, 0) X(bwd_ablate, 0, 1023, 0) X(bwd_fronts, 0, 8, 0) X(fwd_rows, 0, 4, 0)                       \
-  X(chain_fused, 0, 2, 1) X(chain_cc, 0, 2, 0) X(chain_bwd_fused, 0, 1, 1)
-// The knobs that other units read (mlp_fwd.hip, mlp_wide.hip declare them extern): X(key, variable, lo, hi, default).
-//   mlp_variant: Fused producer MLPs: 0 = auto (split-bf16 kernel of mlp_fwd_x3.hip where it applies, else the f32-MFMA kernel
-//     of mlp_fwd.hip with all images LDS-resident when they fit), 1 = f32 MFMA streaming, 2 = f32 MFMA resident, 3 = split-bf16
-//   wide_fuse: wide producer MLPs: second layers of narrow-output MLPs in the forward GEMM's epilogue
-#define PSF_EXTERN_KNOBS(X) X(mlp_variant, psf_g_mlp_variant, 0, 3, 0) X(wide_fuse, psf_g_wide_fuse, 0, 1, 1)
-
-#define X(name, lo, hi, def) std::atomic<int> g_##name{def};
-PSF_KNOBS(X)
+// The knobs: include/psf_chord_tuning.h lists every key with its range, default and meaning. Each row makes an atomic and
+// the row of g_knobs that psf_set_tuning / psf_get_tuning search by name. The chord part is private to this unit: g_<key>,
+// a member of Tuning and its load in snapshot(). The producer part is read by the units that use it (mlp_fwd.hip,
+// mlp_wide.hip declare psf_g_<key> extern) and is no member of Tuning.
+#define X(key, lo, hi, def) std::atomic<int> g_##key{def};
+PSF_TUNING_KNOBS_CHORD(X)
 #undef X
 
 }  // namespace
-#define X(key, var, lo, hi, def) std::atomic<int> var{def};
-PSF_EXTERN_KNOBS(X)
+#define X(key, lo, hi, def) std::atomic<int> psf_g_##key{def};
+PSF_TUNING_KNOBS_PRODUCER(X)
 #undef X
 namespace {
 
@@ -103,11 +68,11 @@ struct Knob {
   int lo, hi;
 };
 Knob g_knobs[] = {
-#define X(name, lo, hi, def) {#name, &g_##name, lo, hi},
-    PSF_KNOBS(X)
+#define X(key, lo, hi, def) {#key, &g_##key, lo, hi},
+    PSF_TUNING_KNOBS_CHORD(X)
 #undef X
-#define X(key, var, lo, hi, def) {#key, &var, lo, hi},
-    PSF_EXTERN_KNOBS(X)
+#define X(key, lo, hi, def) {#key, &psf_g_##key, lo, hi},
+    PSF_TUNING_KNOBS_PRODUCER(X)
 #undef X
 };
 
@@ -115,16 +80,16 @@ Knob g_knobs[] = {
 // a psf_set_tuning from another thread changes the next call, never the middle of one; `walk_backwards` (zigzag of a chain's
 // odd steps) travels in it too instead of in thread-local state.
 struct Tuning {
-#define X(name, lo, hi, def) int name;
-  PSF_KNOBS(X)
+#define X(key, lo, hi, def) int key;
+  PSF_TUNING_KNOBS_CHORD(X)
 #undef X
   bool walk_backwards;
 };
 
 Tuning snapshot() {
   Tuning t;
-#define X(name, lo, hi, def) t.name = g_##name.load();
-  PSF_KNOBS(X)
+#define X(key, lo, hi, def) t.key = g_##key.load();
+  PSF_TUNING_KNOBS_CHORD(X)
 #undef X
   t.walk_backwards = false;
   return t;
@@ -682,7 +647,6 @@ int bwd_impl(const Tuning& tn, const T* dZ, const T* W, const T* V, T* dW, T* dV
       a.V2 = V;
       a.out2 = dW;
       a.wg_per_cu = p.wg_per_cu;
-      if (!bf && !edge) a.ablate = tn.bwd_ablate;
       if (int rc = make_geom(tn, B, N, L, C, VECW, p.fpk.tgs, p.fpk.TR, false, v_batch_stride, 0,
                              p.fpk.tiles_full + (p.fpk.ragged ? 1 : 0), &a.gm))
         return rc;
@@ -1236,7 +1200,7 @@ int psf_mixer_fwd_in_f32(const psf_mixer_input* in, int64_t B, int64_t N, int32_
     fa.nu = first_unit[1] - first_unit[0];
     fa.E = E;
     fa.offs = offs;
-    fa.wg_per_cu = fa.ablate = 0;
+    fa.wg_per_cu = 0;
     fa.stream = s;
     const bool edge_all = pk.ragged && pk.all_edge;  // the g kernel needs its predicate only for rows >= N
     const int rc = window_launches(tn, pk, edge_all, B, N, L, C, N * C, false, &fa.gm, &fa.edge,
@@ -1254,7 +1218,6 @@ int psf_mixer_fwd_in_f32(const psf_mixer_input* in, int64_t B, int64_t N, int32_
     fa.E = E;
     fa.offs = offs;
     fa.wg_per_cu = tn.mixer_wg_limit;
-    fa.ablate = tn.mixer_ablate;
     fa.stream = s;
     tn.walk_backwards = (m & 1) != 0;  // zigzag, as chain_impl
     const int rc = window_launches(tn, pk, pk.all_edge, B, N, L, C, N * C, false, &fa.gm, &fa.edge,

@@ -99,6 +99,9 @@ C99_CONSUMER = r"""
 #include <stdio.h>
 #include <string.h>
 #include "psf_chord.h"
+#include "psf_chord_tuning.h"
+
+#define PSF_COUNT(key, lo, hi, def) +1
 
 int main(void) {
   int64_t off[12];
@@ -110,6 +113,8 @@ int main(void) {
   if (strstr(psf_last_error(), "NULL") == NULL) return 5;
   if (psf_chord_spmm_fwd_f32(w, v, NULL, v, 1, 8, 4, 4, 32, NULL, NULL) != PSF_E_ALIAS) return 6;
   if (psf_chord_spmm_fwd_f32(w, v, NULL, w + 1, 1, 0, 4, 4, 0, NULL, NULL) != PSF_E_SHAPE) return 7;
+  if ((0 PSF_TUNING_KNOBS(PSF_COUNT)) != 21) return 8;              /* the catalogue expands in C99 */
+  if (psf_get_tuning("bwd_fused") != 1 || psf_set_tuning("no_such_knob", 0) != PSF_E_TUNING) return 9;
   printf("psf_version=%d offsets[11]=%lld\n", psf_version(), (long long)off[11]);
   return 0;
 }
@@ -117,7 +122,8 @@ int main(void) {
 
 
 def test_header_is_c99_and_a_plain_c_program_links_the_library(lib, tmp_path):
-    """include/psf_chord.h is the boundary, and its consumer need not be Python: the header compiles as strict C99
+    """include/psf_chord.h is the boundary, and its consumer need not be Python: the header (and the knob catalogue beside it,
+    psf_chord_tuning.h) compiles as strict C99
     (-std=c99 -pedantic -Wall -Werror), a C program links libpsf_chord.so and gets the ABI version, the chord offsets of
     Pathfinder's shape (N = 1024, L = 12: offset 2^10 = 0 mod N, the duplicate self link the reference keeps —
     SyntheticExperiments/psf.py:7-32) and the argument-error codes, all before any HIP call."""
@@ -278,6 +284,94 @@ def test_producer_entry_points_validate_before_touching_the_gpu(lib):
     assert s(one, 31, one, 15, 1 << 20, 32, 15, two, None, two, 1 << 30, None) == -2   # ldx < m
     assert s(one, 480, one, 14, 1 << 20, 32, 15, two, None, two, 1 << 30, None) == -2  # ldy < n
     assert b"strides" in lib.psf_last_error()
+
+
+# The keys of the library: the parent's nineteen chord knobs (its twenty-one less the two timing-lab keys, which left with the
+# labs) and the two that the producer entry points read.
+KNOB_KEYS = ["fwd_variant", "bwd_variant", "xcd_remap", "fwd_split", "fwd_wide", "dw_variant", "dv_threads", "bwd_fused",
+             "bwd_fused_wg_limit", "dw_tgs", "fwd_wg_limit", "chain_zigzag", "mixer_wg_limit", "mixer_lds", "bwd_fronts",
+             "fwd_rows", "chain_fused", "chain_cc", "chain_bwd_fused", "mlp_variant", "wide_fuse"]
+
+CATALOGUE_PRINTER = r"""
+#include <stdio.h>
+#include "psf_chord_tuning.h"
+#define PSF_ROW(key, lo, hi, def) printf("%s %d %d %d\n", #key, lo, hi, def);
+int main(void) {
+  PSF_TUNING_KNOBS(PSF_ROW)
+  return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def catalogue(tmp_path_factory):
+    """include/psf_chord_tuning.h as a C consumer sees it: [(key, lo, hi, default)], printed by a strict-C99 program."""
+    import shutil
+    import subprocess
+    cc = shutil.which("gcc") or shutil.which("cc") or "/opt/rocm/llvm/bin/clang"
+    tmp = tmp_path_factory.mktemp("catalogue")
+    (tmp / "rows.c").write_text(CATALOGUE_PRINTER)
+    proc = subprocess.run([cc, "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           str(tmp / "rows.c"), "-o", str(tmp / "rows")], capture_output=True, text=True)
+    assert proc.returncode == 0, proc.stderr
+    out = subprocess.run([str(tmp / "rows")], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0
+    return [(k, int(lo), int(hi), int(d)) for k, lo, hi, d in (line.split() for line in out.stdout.splitlines())]
+
+
+def test_knob_catalogue_is_what_the_library_accepts(lib, catalogue):
+    """Every row of PSF_TUNING_KNOBS against the loaded library: the default is what psf_get_tuning answers, both ends of the
+    range are accepted, one step beyond either end is PSF_E_TUNING and leaves the value alone, and the value is put back."""
+    E_TUNING = -6
+    assert len(catalogue) == len({k for k, *_ in catalogue})  # one entry per key
+    for key, lo, hi, default in catalogue:
+        k = key.encode()
+        assert lo <= default <= hi, key
+        assert lib.psf_get_tuning(k) == default, key
+        try:
+            for v in (lo, hi):
+                assert lib.psf_set_tuning(k, v) == 0 and lib.psf_get_tuning(k) == v, (key, v)
+            for v in (lo - 1, hi + 1):
+                assert lib.psf_set_tuning(k, v) == E_TUNING and lib.psf_get_tuning(k) == hi, (key, v)
+                assert key.encode() in lib.psf_last_error()
+        finally:
+            assert lib.psf_set_tuning(k, default) == 0
+        assert lib.psf_get_tuning(k) == default, key
+
+
+def test_knob_key_set(lib, catalogue):
+    """The catalogue's keys are exactly the 21 written above, and the library knows no other: the two timing-lab keys are
+    rejected exactly like a key that never existed."""
+    E_TUNING = -6
+    assert len(KNOB_KEYS) == 21
+    assert sorted(k for k, *_ in catalogue) == sorted(KNOB_KEYS)
+    for key in KNOB_KEYS:
+        assert lib.psf_get_tuning(key.encode()) >= 0, key
+    answers = {}
+    for key in ("no_such_knob", "mixer_ablate", "bwd_ablate"):
+        rc_set, err_set = lib.psf_set_tuning(key.encode(), 0), lib.psf_last_error().decode()
+        rc_get, err_get = lib.psf_get_tuning(key.encode()), lib.psf_last_error().decode()
+        assert rc_set == E_TUNING and rc_get == E_TUNING, key
+        answers[key] = (rc_set, err_set.replace(key, "KEY"), rc_get, err_get.replace(key, "KEY"))
+    assert answers["mixer_ablate"] == answers["bwd_ablate"] == answers["no_such_knob"]
+    assert "unknown tuning key 'KEY'" in answers["no_such_knob"][1]
+
+
+def test_tuning_context_manager_restores_on_error(lib):
+    import sparsefactorization_amd as sfa
+    assert sfa.tuning is sfa._lib.tuning
+    with sfa.tuning(fwd_variant=1, chain_cc=2):
+        assert (sfa.get_tuning("fwd_variant"), sfa.get_tuning("chain_cc")) == (1, 2)
+    assert (sfa.get_tuning("fwd_variant"), sfa.get_tuning("chain_cc")) == (0, 0)
+    with pytest.raises(ZeroDivisionError):
+        with sfa.tuning(bwd_fused=0):
+            assert sfa.get_tuning("bwd_fused") == 0
+            1 / 0
+    assert sfa.get_tuning("bwd_fused") == 1
+    with pytest.raises(sfa.PSFLibraryError):  # a refused value: what was set before it is put back
+        with sfa.tuning(fwd_variant=2, bwd_variant=7):
+            pass
+    assert (sfa.get_tuning("fwd_variant"), sfa.get_tuning("bwd_variant")) == (0, 0)
 
 
 def test_tuning_knobs(lib):

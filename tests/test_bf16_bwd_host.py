@@ -1,6 +1,7 @@
 """CPU: the host side of the bf16 fused backward step and of the bf16 backward chain entry (csrc/bwd_fused_bf16.h,
 psf_chord.hip: pick_fused_step_bf16, psf_chord_chain_bwd_bf16, psf_describe_bwd). psf_describe_bwd names the kernel(s) a
 backward step would run; the chain entry's argument checks are reached before anything is launched. No device is touched."""
+import contextlib
 import ctypes
 import os
 import re
@@ -23,15 +24,9 @@ def lib():
 @pytest.fixture
 def knobs(lib):
     """Set tuning knobs for one test; restored afterwards."""
-    saved = {}
-
-    def set_(key, value):
-        saved.setdefault(key, lib.psf_get_tuning(key.encode()))
-        assert lib.psf_set_tuning(key.encode(), value) == 0
-
-    yield set_
-    for key, value in saved.items():
-        lib.psf_set_tuning(key.encode(), value)
+    from sparsefactorization_amd import _lib
+    with contextlib.ExitStack() as stack:
+        yield lambda key, value: stack.enter_context(_lib.tuning(**{key: value}))
 
 
 def _describe(lib, B, N, L, C, elem_bytes):

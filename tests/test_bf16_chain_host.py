@@ -1,5 +1,6 @@
 """CPU: the planner and the describe entry of the bf16 one-launch forward chain (csrc/fwd_chain_lds_bf16.h).
 psf_describe_chain_fwd_dtype names the kernel a chain would run; nothing is launched."""
+import contextlib
 import ctypes
 import os
 import re
@@ -17,15 +18,9 @@ def lib():
 @pytest.fixture
 def knobs(lib):
     """Set tuning knobs for one test; restored afterwards."""
-    saved = {}
-
-    def set_(key, value):
-        saved.setdefault(key, lib.psf_get_tuning(key.encode()))
-        assert lib.psf_set_tuning(key.encode(), value) == 0
-
-    yield set_
-    for key, value in saved.items():
-        lib.psf_set_tuning(key.encode(), value)
+    from sparsefactorization_amd import _lib
+    with contextlib.ExitStack() as stack:
+        yield lambda key, value: stack.enter_context(_lib.tuning(**{key: value}))
 
 
 def _describe(lib, B, N, L, C, M, elem_bytes):

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from oracle import chord_oracle as oc
+from sparsefactorization_amd._lib import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -54,24 +55,6 @@ def _assert_dw(got, want_f32):
     assert (err <= bound).all(), f"dW off by up to {(err / np.maximum(bound, 1e-30)).max():.2f} x the bound"
 
 
-class _Knobs:
-    """Set tuning knobs; everything is put back on exit."""
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        import sparsefactorization_amd as sfa
-        self.saved = {k: sfa._lib.get_tuning(k) for k in self.kv}
-        for k, v in self.kv.items():
-            sfa.set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        import sparsefactorization_amd as sfa
-        for k, v in self.saved.items():
-            sfa.set_tuning(k, v)
-
-
 def _step(dZ, W, V, B, N, L, C, stride, offsets=None, dW=None, dV=None):
     """One backward step on device tensors (both gradients), outputs pre-filled with NaN."""
     from sparsefactorization_amd.chord import _launch_bwd
@@ -94,10 +77,10 @@ def _check_three(gpu, B, N, L, C, seed, fused_knob, offsets=None, broadcast=Fals
         dWbuf = torch.empty(B * N * L + shift, dtype=torch.bfloat16, device=gpu)[shift:].view(B, N, L)
         assert Wt.data_ptr() % 16 != 0 and dWbuf.data_ptr() % 16 != 0
     stride = 0 if broadcast else N * C
-    with _Knobs(bwd_fused=fused_knob, **(knobs or {})):
+    with tuning(bwd_fused=fused_knob, **(knobs or {})):
         dW1, dV1 = _step(dZt, Wt, Vt, B, N, L, C, stride, offsets, dW=dWbuf)
         dW1, dV1 = dW1.clone(), dV1.clone()
-    with _Knobs(bwd_fused=0):
+    with tuning(bwd_fused=0):
         dW0, dV0 = _step(dZt, Wt, Vt, B, N, L, C, stride, offsets, dW=dWbuf)
     dF, dVo = oc.spmul_bwd(dZ, W, np.ascontiguousarray(np.broadcast_to(V, (B, N, C))), offsets)
     _same_bits(dV1, _rne(dVo), "dV against the oracle")
@@ -122,7 +105,7 @@ ALIGNED = [
 @pytest.mark.parametrize("B,N,L,C", ALIGNED)
 def test_aligned_instance(gpu, B, N, L, C):
     import sparsefactorization_amd as sfa
-    with _Knobs(bwd_fused=2):
+    with tuning(bwd_fused=2):
         name = sfa._lib.describe_bwd(B, N, L, C, elem_bytes=2)
     assert name.startswith(f"chord_bwd_fused_k<bf16,L={L},TG={C // 8},NT=256> TR={2048 // C} "), name
     _check_three(gpu, B, N, L, C, 100, 2)
@@ -147,7 +130,7 @@ def test_knobs_do_not_change_bits(gpu, knob, values):
     B, N, L, C = 4, 16384, 15, 8
     outs = []
     for v in values:
-        with _Knobs(bwd_fused=2, **{knob: v}):
+        with tuning(bwd_fused=2, **{knob: v}):
             assert "chord_bwd_fused_k<bf16" in sfa._lib.describe_bwd(B, N, L, C, elem_bytes=2)
         outs.append(_check_three(gpu, B, N, L, C, 130, 2, knobs={knob: v}))
     for dW, dV in outs[1:]:
@@ -176,9 +159,9 @@ def test_nan_and_inf(gpu):
         flat = arr.reshape(-1)
         flat[rng.choice(flat.size, 6, replace=False)] = np.resize(np.array(vals, dtype=np.float32), 6)
     Wt, Vt, dZt = _bt(W, gpu), _bt(V, gpu), _bt(dZ, gpu)
-    with _Knobs(bwd_fused=2):
+    with tuning(bwd_fused=2):
         dW1, dV1 = [t.clone() for t in _step(dZt, Wt, Vt, B, N, L, C, N * C)]
-    with _Knobs(bwd_fused=0):
+    with tuning(bwd_fused=0):
         dW0, dV0 = _step(dZt, Wt, Vt, B, N, L, C, N * C)
     assert bool(torch.isnan(dV0).any()) and bool(torch.isnan(dW0).any())
     _same_bits(dV1, dV0, "dV")
@@ -193,9 +176,9 @@ def test_after_nan_in_every_lds(gpu, B, N, L, C):
     from test_gpu_stale_lds import _poison
     W, V, dZ = _mk((B, N, L), 170), _mk((B, N, C), 171), _mk((B, N, C), 172)
     Wt, Vt, dZt = _bt(W, gpu), _bt(V, gpu), _bt(dZ, gpu)
-    with _Knobs(bwd_fused=0):
+    with tuning(bwd_fused=0):
         dW0, dV0 = _step(dZt, Wt, Vt, B, N, L, C, N * C)
-    with _Knobs(bwd_fused=2):
+    with tuning(bwd_fused=2):
         dWb, dVb = torch.empty_like(Wt), torch.empty_like(Vt)
         _poison(gpu)
         dW1, dV1 = _step(dZt, Wt, Vt, B, N, L, C, N * C, dW=dWb, dV=dVb)
@@ -242,7 +225,7 @@ def _entry_chain(gpu, Ws, V0, dOut, residual, B, N, L, C):
 def test_chain_entry_matches_the_per_step_loop(gpu, B, N, L, C, M, residual):
     from sparsefactorization_amd import _lib
     Ws, V0, dOut = _chain_operands(gpu, B, N, L, C, M, 200)
-    with _Knobs(chain_bwd_fused=0):  # the entry returns PSF_E_UNSUPPORTED: chord.py's own loop
+    with tuning(chain_bwd_fused=0):  # the entry returns PSF_E_UNSUPPORTED: chord.py's own loop
         rc, _ = _entry_chain(gpu, Ws, V0, dOut, residual, B, N, L, C)
         assert rc == _lib.PSF_E_UNSUPPORTED
         loop = _autograd_chain(Ws, V0, dOut, residual)
@@ -291,7 +274,7 @@ def test_chain_falls_back_when_the_residual_sum_is_outside_its_limits(gpu):
     # without the residual there is no sum: the entry takes odd sizes too
     rc, direct = _entry_chain(gpu, Ws, V0, dOut, False, B, N, L, C)
     assert rc == 0
-    with _Knobs(chain_bwd_fused=0):
+    with tuning(chain_bwd_fused=0):
         loop = _autograd_chain(Ws, V0, dOut, False)
     for a, b in zip(loop, direct):
         _same_bits(b, a)

@@ -6,13 +6,13 @@ compared as int16 bits. Every case first asserts, through describe_chain_fwd(...
 the kernel it means to test is the one that runs, asserts that the expected values are finite (no case passes as NaN == NaN;
 NaN and Inf have a case of their own), and also runs the per-step route (chain_fused = 0) and asserts equal bits."""
 import ctypes
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import chord_oracle as oc
+from sparsefactorization_amd._lib import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -61,19 +61,6 @@ def _assert_same(got, want, what):
     assert bad == 0, f"{what}: {bad} elements differ"
 
 
-@contextmanager
-def _knobs(**kv):
-    import sparsefactorization_amd as sfa
-    old = {k: sfa.get_tuning(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            sfa.set_tuning(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            sfa.set_tuning(k, v)
-
-
 def _run_both_modes(Wt, V0t, residual, want, what, offsets=None):
     """Ping-pong storage (no_grad) and every step kept; each stored step is checked, not only the last."""
     import sparsefactorization_amd as sfa
@@ -99,11 +86,11 @@ def _check_case(gpu, B, N, M, L, C, residual, cc, kernel, seed=200):
     want = _chain_ref_steps(Ws, V0, residual)
     _assert_finite(want)
     Wt, V0t = [_bt(w, gpu) for w in Ws], _bt(V0, gpu)
-    with _knobs(chain_fused=2, chain_cc=cc):
+    with tuning(chain_fused=2, chain_cc=cc):
         desc = _lib.describe_chain_fwd(B, N, L, C, M, elem_bytes=2)
         assert desc.startswith(kernel), desc
         one = _run_both_modes(Wt, V0t, residual, want, kernel)
-    with _knobs(chain_fused=0):
+    with tuning(chain_fused=0):
         assert "chain" not in _lib.describe_chain_fwd(B, N, L, C, M, elem_bytes=2)
         steps = _run_both_modes(Wt, V0t, residual, want, "per-step route")
     assert torch.equal(_bits(one[0]), _bits(steps[0]))
@@ -163,10 +150,10 @@ def test_nan_and_inf_propagate_like_the_per_step_route(gpu, B, N, M, L, C, cc, k
     want = _chain_ref_steps(Ws, V0, residual)
     assert bool(torch.isnan(want[-1]).any()) and not bool(torch.isnan(want[-1]).all())
     Wt, V0t = [_bt(w, gpu) for w in Ws], _bt(V0, gpu)
-    with _knobs(chain_fused=2, chain_cc=cc):
+    with tuning(chain_fused=2, chain_cc=cc):
         assert _lib.describe_chain_fwd(B, N, L, C, M, elem_bytes=2).startswith(kernel)
         _run_both_modes(Wt, V0t, residual, want, kernel)
-    with _knobs(chain_fused=0):
+    with tuning(chain_fused=0):
         _run_both_modes(Wt, V0t, residual, want, "per-step route")
 
 
@@ -181,10 +168,10 @@ def test_broadcast_v0(gpu, B, N, M, L, C, cc, kernel):
     want = _chain_ref_steps(Ws, E, False)
     _assert_finite(want)
     Wt, Et = [_bt(w, gpu) for w in Ws], _bt(E, gpu)
-    with _knobs(chain_fused=2, chain_cc=cc):
+    with tuning(chain_fused=2, chain_cc=cc):
         assert _lib.describe_chain_fwd(B, N, L, C, M, elem_bytes=2).startswith(kernel)
         one = _run_both_modes(Wt, Et, False, want, kernel)
-    with _knobs(chain_fused=0):
+    with tuning(chain_fused=0):
         steps = _run_both_modes(Wt, Et, False, want, "per-step route")
     assert torch.equal(_bits(one[0]), _bits(steps[0]))
 
@@ -201,10 +188,10 @@ def test_explicit_and_negative_offsets(gpu, B, N, M, C, cc, off, kernel):
     want = _chain_ref_steps(Ws, V0, True, off)
     _assert_finite(want)
     Wt, V0t = [_bt(w, gpu) for w in Ws], _bt(V0, gpu)
-    with _knobs(chain_fused=2, chain_cc=cc):
+    with tuning(chain_fused=2, chain_cc=cc):
         assert _lib.describe_chain_fwd(B, N, L, C, M, elem_bytes=2).startswith(kernel)
         one = _run_both_modes(Wt, V0t, True, want, kernel, off)
-    with _knobs(chain_fused=0):
+    with tuning(chain_fused=0):
         steps = _run_both_modes(Wt, V0t, True, want, "per-step route", off)
     assert torch.equal(_bits(one[0]), _bits(steps[0]))
 
@@ -230,7 +217,7 @@ def test_w_at_an_odd_two_byte_offset(gpu, B, N, M, L, C, cc, shift):
     Wt = [_shifted(_bt(w, gpu), shift) for w in Ws]
     assert all(w.data_ptr() % 4 == 2 for w in Wt)
     Wt[1] = _bt(Ws[1], gpu)  # (one step's W aligned: the parity is per step)
-    with _knobs(chain_fused=2, chain_cc=cc):
+    with tuning(chain_fused=2, chain_cc=cc):
         _run_both_modes(Wt, _bt(V0, gpu), True, want, f"W shifted by {shift}")
 
 
@@ -242,7 +229,7 @@ def test_v0_off_its_16_byte_boundary_takes_the_per_step_route(gpu, B, N, M, L, C
     _assert_finite(want)
     V0t = _shifted(_bt(V0, gpu), 1)
     assert V0t.data_ptr() % 16 == 2
-    with _knobs(chain_fused=2, chain_cc=cc):
+    with tuning(chain_fused=2, chain_cc=cc):
         _run_both_modes([_bt(w, gpu) for w in Ws], V0t, True, want, "V0 shifted")
 
 
@@ -258,7 +245,7 @@ def test_edges_of_the_product_range(gpu, scale, B, N, L, C, cc, kernel):
     V0 = pos(900, (B, N, C), scale)
     want = _chain_ref_steps(Ws, V0, False)
     _assert_finite(want)
-    with _knobs(chain_fused=2, chain_cc=cc):
+    with tuning(chain_fused=2, chain_cc=cc):
         assert _lib.describe_chain_fwd(B, N, L, C, 2, elem_bytes=2).startswith(kernel)
         _run_both_modes([_bt(w, gpu) for w in Ws], _bt(V0, gpu), False, want, f"scale={scale}")
 
@@ -268,7 +255,7 @@ def test_two_identical_runs_give_identical_bits(gpu):
     for (B, N, M, L, C, cc) in [(4, 1024, 10, 11, 32, 0), (4, 2000, 6, 12, 64, 2), (2, 4097, 5, 14, 16, 2)]:
         Wt = [_bt(_mk((B, N, L), 951 + m, 0.3), gpu) for m in range(M)]
         V0t = _bt(_mk((B, N, C), 950), gpu)
-        with _knobs(chain_fused=2, chain_cc=cc), torch.no_grad():
+        with tuning(chain_fused=2, chain_cc=cc), torch.no_grad():
             a = sfa.chord_chain(Wt, V0t, True).clone()
             b = sfa.chord_chain(Wt, V0t, True).clone()
         assert bool(torch.isfinite(a.float()).all())
@@ -283,7 +270,7 @@ def test_default_route_on_the_lra_shapes(gpu, B, N, M, L, C):
     V0 = _mk((B, N, C), 1000)
     want = _chain_ref_steps(Ws, V0, True)
     _assert_finite(want)
-    with _knobs(chain_fused=1, chain_cc=0):
+    with tuning(chain_fused=1, chain_cc=0):
         _run_both_modes([_bt(w, gpu) for w in Ws], _bt(V0, gpu), True, want, "default route")
 
 
@@ -308,7 +295,7 @@ def test_nothing_outside_the_results_is_written(gpu, B, N, M, L, C, cc, kernel):
     lib = _lib.load()
     w_tab = (ctypes.c_void_p * M)(*[w.data_ptr() for w in Wt])
     o_tab = (ctypes.c_void_p * M)(*[o.data_ptr() for o in outs])
-    with _knobs(chain_fused=2, chain_cc=cc):
+    with tuning(chain_fused=2, chain_cc=cc):
         assert _lib.describe_chain_fwd(B, N, L, C, M, elem_bytes=2).startswith(kernel)
         with torch.cuda.device(gpu):
             rc = lib.psf_chord_chain_fwd_bf16(w_tab, V0t.data_ptr(), o_tab, M, 1, B, N, L, C, N * C, None, _stream_ptr(gpu))

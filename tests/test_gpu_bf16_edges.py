@@ -23,6 +23,7 @@ import torch
 
 import bf16_edges as be
 from oracle import chord_oracle as oc
+from sparsefactorization_amd._lib import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -81,24 +82,6 @@ def _kernel(what, L, spec):
     if kind == "gen":
         return f"chord_{what}_generic_k<bf16,VEC={n}>"
     return f"chord_{what}_win_k<bf16,L={L},TG={n},R={1 if what == 'dw' else 2},NT=256>"
-
-
-class _Knobs:
-    """Set tuning knobs; everything is put back on exit."""
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        from sparsefactorization_amd import _lib
-        self.saved = {k: _lib.get_tuning(k) for k in self.kv}
-        for k, v in self.kv.items():
-            _lib.set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        from sparsefactorization_amd import _lib
-        for k, v in self.saved.items():
-            _lib.set_tuning(k, v)
 
 
 def _assert_routes(B, N, L, C):
@@ -208,7 +191,7 @@ def _guard_band_case(gpu, B, N, L, C, wshift, vshift, offsets=None):
     for fused, want_dw, want_dv in ((0, True, True), (2, True, True), (0, True, False), (0, False, True)):
         gw = _arena((B, N, L), gpu, wshift) if want_dw else None
         gv = _arena((B, N, C), gpu, vshift) if want_dv else None
-        with _Knobs(bwd_fused=fused):
+        with tuning(bwd_fused=fused):
             if wshift == vshift == 0 and offsets is None and want_dw and want_dv:
                 _assert_routes(B, N, L, C)
             _launch_bwd(dZt, Wt, Vt, gw and gw[1], gv and gv[1], B, N, L, C, N * C, off)
@@ -272,7 +255,7 @@ def test_steps_after_nan_in_every_lds(gpu, B, N, L, C):
     for fused in (0, 2):
         gW = torch.full((B, N, L), float("nan"), device=gpu, dtype=torch.bfloat16)
         gV = torch.full((B, N, C), float("nan"), device=gpu, dtype=torch.bfloat16)
-        with _Knobs(bwd_fused=fused):
+        with tuning(bwd_fused=fused):
             _assert_routes(B, N, L, C)
             _poison(gpu)
             _launch_bwd(dZt, Wt, Vt, gW, gV, B, N, L, C, N * C, None)
@@ -293,7 +276,7 @@ def test_dw_known_answers_bit_for_bit(gpu, shape, fused, broadcast):
     Wt, Vt, dZt = _bt(W, gpu), _bt(V, gpu), _bt(dZ, gpu)
     gW = torch.full((B, N, L), float("nan"), device=gpu, dtype=torch.bfloat16)
     gV = torch.full((B, N, C), float("nan"), device=gpu, dtype=torch.bfloat16)
-    with _Knobs(bwd_fused=fused):
+    with tuning(bwd_fused=fused):
         _assert_routes(B, N, L, C)
         _launch_bwd(dZt, Wt, Vt, gW, gV, B, N, L, C, 0 if broadcast else N * C, None)
     _assert_bits(_bits(gW), be.rne_bits(exact.astype(np.float32)), "dW")
@@ -307,7 +290,7 @@ def test_dw_random_data_inside_the_float64_bracket(gpu, B, N, L, C, bwd_variant,
     ref = _ref(B, N, L, C)
     print(f"share of brackets with more than one value at C={C}: {ref.loose:.2%}")
     gW = torch.full((B, N, L), float("nan"), device=gpu, dtype=torch.bfloat16)
-    with _Knobs(bwd_fused=fused, bwd_variant=bwd_variant):
+    with tuning(bwd_fused=fused, bwd_variant=bwd_variant):
         _assert_routes(B, N, L, C)
         _launch_bwd(_bt(ref.dZ, gpu), _bt(ref.W, gpu), _bt(ref.V, gpu), gW, None, B, N, L, C, N * C, None)
     _assert_dw_ref(_bits(gW), ref, "dW")
@@ -341,7 +324,7 @@ def test_special_values_on_every_route(gpu, B, N, L, C, run):
     assert safe.sum() >= 8 and np.isnan(dF).any() and np.isinf(dF).any() and np.isnan(dV).any()
     Wt, Vt, Rt, dZt = (_bt(a, gpu) for a in (W, V, R, dZ))
     for variant in (0, 1):
-        with _Knobs(fwd_variant=variant):
+        with tuning(fwd_variant=variant):
             _assert_routes(B, N, L, C)
             for res, want in ((None, want_out), (Rt, want_outR)):
                 got = torch.full((B, N, C), float("nan"), device=gpu, dtype=torch.bfloat16)
@@ -350,7 +333,7 @@ def test_special_values_on_every_route(gpu, B, N, L, C, run):
     for bwd_variant, fused in ((0, 1), (0, 0), (0, 2), (1, 1)):
         gW = torch.zeros((B, N, L), device=gpu, dtype=torch.bfloat16)
         gV = torch.zeros((B, N, C), device=gpu, dtype=torch.bfloat16)
-        with _Knobs(bwd_variant=bwd_variant, bwd_fused=fused):
+        with tuning(bwd_variant=bwd_variant, bwd_fused=fused):
             _assert_routes(B, N, L, C)
             _launch_bwd(dZt, Wt, Vt, gW, gV, B, N, L, C, N * C, None)
         what = f"bwd_variant={bwd_variant} bwd_fused={fused}"
@@ -377,7 +360,7 @@ def test_limit_shapes(gpu, B, N, L, C):
     for fused in (0, 2):
         gW = torch.full((B, N, L), float("nan"), device=gpu, dtype=torch.bfloat16)
         gV = torch.full((B, N, C), float("nan"), device=gpu, dtype=torch.bfloat16)
-        with _Knobs(bwd_fused=fused):
+        with tuning(bwd_fused=fused):
             _assert_routes(B, N, L, C)
             _launch_bwd(dZt, Wt, Vt, gW, gV, B, N, L, C, N * C, None)
         _assert_bits(_bits(gV), ref.dV, f"dV, bwd_fused={fused}")

@@ -28,6 +28,7 @@ import torch
 
 import bf16_edges as be
 from oracle import chord_oracle as oc
+from sparsefactorization_amd._lib import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -53,24 +54,6 @@ FAMILIES = {
 B, M = 2, 2  # batch elements; steps of a chain
 
 
-class _Knobs:
-    """Set tuning knobs; everything is put back on exit."""
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        from sparsefactorization_amd import _lib
-        self.saved = {k: _lib.get_tuning(k) for k in self.kv}
-        for k, v in self.kv.items():
-            _lib.set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        from sparsefactorization_amd import _lib
-        for k, v in self.saved.items():
-            _lib.set_tuning(k, v)
-
-
 def _describe(family, N, L, batch=B, C=None):
     from sparsefactorization_amd import _lib
     entry, eb, C0, _knobs, _subs = FAMILIES[family]
@@ -94,7 +77,7 @@ ROUTE_DEFAULTS = {"fwd_variant": 0, "bwd_variant": 0, "fwd_split": 1, "fwd_wide"
 @functools.lru_cache(maxsize=None)
 def _smallest_n(family, L, also=(), batch=B, C=None):
     """The smallest N at which describe names the family's kernel for L (and every string of `also`), or None. Host only."""
-    with _Knobs(**{**ROUTE_DEFAULTS, **FAMILIES[family][3]}):
+    with tuning(**{**ROUTE_DEFAULTS, **FAMILIES[family][3]}):
         for N in range(1, N_MAX + 1):
             if _names(family, _describe(family, N, L, batch, C), L, also):
                 return N
@@ -190,7 +173,7 @@ def test_forward_window_every_link_count(gpu, family, L):
     _e, eb, C, knobs, _s = FAMILIES[family]
     aligned = ("tiles=full, aligned",)
     N = _smallest_n(family, L, aligned)
-    with _Knobs(**knobs):
+    with tuning(**knobs):
         _confirm(family, N, L, aligned)
         _fwd_case(gpu, eb, N, L, C, None, f"{family} L={L} N={N} aligned")
         s = _confirm(family, N + 1, L)
@@ -210,7 +193,7 @@ def test_forward_window_every_link_count(gpu, family, L):
 def _full_mode_shape(family, L):
     """(C, N): the narrowest rows, then the shortest sequence, whose aligned launch has a far link; None where there is none
     (two tiles are at most 1024 rows, so N is walked to 2048)."""
-    with _Knobs(**{**ROUTE_DEFAULTS, **FAMILIES[family][3]}):
+    with tuning(**{**ROUTE_DEFAULTS, **FAMILIES[family][3]}):
         for C in (8, 16, 32, 64, 128, 256):
             for N in range(1, 2049):
                 s = _describe(family, N, L, B, C)
@@ -225,7 +208,7 @@ def _full_mode_shape(family, L):
 def test_backward_steps_every_link_count(gpu, family, batch, L):
     _e, eb, C, knobs, _s = FAMILIES[family]
     N = _smallest_n(family, L, (), batch)
-    with _Knobs(**knobs):
+    with tuning(**knobs):
         _confirm(family, N, L, (), batch)
         _bwd_case(gpu, eb, batch, N, L, C, f"{family} B={batch} L={L} N={N}")
 
@@ -235,7 +218,7 @@ def test_backward_steps_every_link_count(gpu, family, batch, L):
 def test_forward_chain_every_link_count(gpu, family, L):
     _e, eb, C, knobs, _s = FAMILIES[family]
     N = _smallest_n(family, L)
-    with _Knobs(**knobs):
+    with tuning(**knobs):
         _confirm(family, N, L)
         _chain_case(gpu, eb, N, L, C, f"{family} L={L} N={N}")
 
@@ -295,7 +278,7 @@ def test_mixer_step_kernel_every_link_count(gpu, L):
     E, h, C = 32, 32, 8
     hs = (ctypes.c_int32 * (M + 1))(*[h] * (M + 1))
     plan = lambda n, l: _lib.load().psf_mixer_fwd_plan(n, E, M, hs, C, l)  # noqa: E731
-    with _Knobs(mixer_lds=0):
+    with tuning(mixer_lds=0):
         N = next(n for n in range(1, N_MAX + 1) if plan(n, min(max(L, 4), 20)) == 1)
         assert plan(N, L) == (1 if 4 <= L <= 20 else 0)
         g, fs = _blocks(E, h, C, L, M, seed=11)
@@ -330,7 +313,7 @@ def test_one_link_count_outside_the_compiled_range(gpu, family, L):
         return
     entry, eb, C, knobs, _s = FAMILIES[family]
     N = _smallest_n(family, L + 1 if L < 4 else L - 1)
-    with _Knobs(**knobs):
+    with tuning(**knobs):
         assert not _names(family, _describe(family, N, L), L)
         if entry == "fwd":
             _fwd_case(gpu, eb, N, L, C, None, f"{family} L={L} N={N}")
@@ -356,7 +339,7 @@ def _child(gpu):
     shapes = {"fwd_f32": _smallest_n("fwd_f32", L, ("tiles=full, aligned",)), "fused_f32": _smallest_n("fused_f32", L),
               "fused_bf16": _smallest_n("fused_bf16", L)}
     for limit in (3, 2, 3):
-        with _Knobs(fwd_wg_limit=limit, bwd_fused_wg_limit=limit, bwd_fused=2):
+        with tuning(fwd_wg_limit=limit, bwd_fused_wg_limit=limit, bwd_fused=2):
             assert _lib.get_tuning("fwd_wg_limit") == limit and _lib.get_tuning("bwd_fused_wg_limit") == limit
             for family, N in shapes.items():
                 assert _confirm(family, N, L).startswith(want_name[family])
@@ -365,7 +348,7 @@ def _child(gpu):
                     _fwd_case(gpu, 4, N, L, C, None, f"forward, limit {limit}")
                 else:
                     _bwd_case(gpu, FAMILIES[family][1], B, N, L, C, f"{family}, limit {limit}")
-    with _Knobs(chain_fused=2):
+    with tuning(chain_fused=2):
         for N, lds in ((600, 38400), (1000, 64000)):  # 2 buffers x 2 N slots x 16 bytes on chord_chain_lds_k<L, 2, 2, RES, 1024>
             s = _confirm("chain_f32", N, L, ("CC=2,R=2",))
             assert int(re.search(r"(\d+) threads", s).group(1)) > 512 and 2 * 2 * N * 16 == lds, s
