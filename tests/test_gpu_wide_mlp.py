@@ -52,6 +52,9 @@ WIDE_CASES = [  # (T, E, [(h, out), ...])
     (1000, 48, [(96, 33), (33, 1), (128, 20)]),      # ragged token count, odd widths, outputs not multiples of 4
     (255, 16, [(5, 3)]),                             # smaller than one GEMM tile
     (257, 512, [(128, 128), (100, 127)]),            # one token past a tile, two wide outputs
+    (257, 144, [(64, 12), (127, 33)]),               # the first width on the 256 x 256 GEMM configuration: the most padding
+    (257, 528, [(100, 17)]),                         # E past 512: three column tiles in dX / dAcat, one partial
+    (257, 1024, [(128, 12), (64, 128)]),             # WIDE_MAX_E: E_pad = 1024, four column tiles
 ]
 
 

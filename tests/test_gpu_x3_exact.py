@@ -9,8 +9,9 @@ test_x3_exact_cpu.py show that emulations of such defects change these answers).
 Paths: psf_mlp_fwd_f32 (mlp_variant 1, 2, 3), psf_mlp_bwd_f32 (with and without dX), psf_mlp_wide_fwd_f32 /
 psf_mlp_wide_bwd_f32 (wide_fuse 0 and 1) and psf_mixer_fwd_f32 (the per-step kernels and the single-launch mixer_lds).
 
-Not covered here: accuracy on random data is still held by the max-normalised bounds of test_gpu_producer.py and
-test_gpu_wide_mlp.py; per-row / per-column error on 2^k-scaled rows against a derived componentwise bound is open.
+Not covered here: dense operands through the curved part of GELU. The max-normalised bounds of test_gpu_producer.py and
+test_gpu_wide_mlp.py hold them per tensor; test_gpu_x3_scaled.py (tests/x3_scaled.py, self-tests in test_x3_scaled_cpu.py)
+holds every element against its own scale on 2^k-scaled tokens, columns, hidden rows and outputs, and the 2^k scaling laws.
 """
 import numpy as np
 import pytest
