@@ -161,7 +161,8 @@ int psf_chord_spmm_fwd_f64(const double* W, const double* V, const double* res, 
  *                 otherwise M per-step launches. psf_describe_chain_fwd_dtype names the route.
  *                 Backward chain: psf_chord_chain_bwd_bf16 issues the per-step launches and the one residual sum inside
  *                 the library (below).
- * Not covered: float16, mixed dtypes, the bf16 producer / mixer / flat-head entries, a one-launch bf16 backward chain, and
+ *                 Producer MLPs, forward (inference): psf_mlp_fwd_bf16 (below, next to psf_mlp_fwd_f32).
+ * Not covered: float16, mixed dtypes, the bf16 mixer / flat-head entries, the bf16 producer backward, a one-launch bf16 backward chain, and
  *                 an edge instance of the bf16 fused backward step (ragged N, other far offsets, W / dW off their 16-byte
  *                 boundary: those steps run the dW and dV window kernels).
  */
@@ -361,6 +362,30 @@ int64_t psf_mlp_fwd_workspace(int32_t E, int32_t K, const int32_t* h, const int3
 int psf_mlp_fwd_f32(const float* X, int64_t T, int32_t E, int32_t K, const float* const* A, const float* const* a,
                     const float* const* B, const float* const* b, const int32_t* h, const int32_t* O,
                     float* const* Y, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
+ * The same for a bf16 model (raw bits), in one launch plus the packing of the weights: table conventions, validation order
+ * and error codes as psf_mlp_fwd_f32. Added without a version change (PSF_ABI_VERSION: the bf16 entries are additive).
+ * Arithmetic, for k < K — every operand and result is bf16, exactly the three roundings of nn.Linear -> nn.GELU() ->
+ * nn.Linear on bf16 tensors:
+ *     z[t,j]    = bf16_rne( f32( sum_e X[t,e] * A[k][j,e] + a[k][j] ) )
+ *     h[t,j]    = bf16_rne( GELU_f32( z[t,j] ) )                       erf GELU; Phi is evaluated to 7.5e-8 absolute
+ *     Y[k][t,o] = bf16_rne( f32( sum_j h[t,j] * B[k][o,j] + b[k][o] ) )
+ *   Products of bf16 values are exact in f32; the sums are accumulated in f32 on the matrix pipe (one
+ *   v_mfma_f32_32x32x16_bf16 term per product) in an unspecified order. The result therefore differs from the layer-by-layer
+ *   evaluation only where an f32 sum lands on a bf16 rounding tie. A NaN stays a NaN; a token's outputs depend on that
+ *   token's row of X only. The hidden layer never reaches memory: X is read once, each Y[k] is written once.
+ *   Limits: E a multiple of 8, 8 <= E <= 64; 1 <= h[k] <= 128; 1 <= O[k] <= 32; 1 <= K <= 32; T >= 1; X and every Y[k]
+ *   16-byte aligned (PSF_E_ALIGN), weights and biases 2-byte aligned. Nothing outside Y[k][0 .. T*O[k]) is written, for odd
+ *   O[k] and ragged T too. `workspace`: caller-owned, 16-byte-aligned device scratch of at least
+ *   psf_mlp_fwd_bf16_workspace(E, K, h, O) bytes (6912 per 32 hidden rows of each MLP; -1: unsupported sizes). No allocation,
+ *   no synchronisation; capturable in a HIP graph. Wider layers (E >= 128, O = 128: the LRA networks), training and the
+ *   backward are not covered.
+ */
+int64_t psf_mlp_fwd_bf16_workspace(int32_t E, int32_t K, const int32_t* h, const int32_t* O);
+int psf_mlp_fwd_bf16(const uint16_t* X, int64_t T, int32_t E, int32_t K, const uint16_t* const* A, const uint16_t* const* a,
+                     const uint16_t* const* B, const uint16_t* const* b, const int32_t* h, const int32_t* O,
+                     uint16_t* const* Y, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * The mixer with W produced INSIDE the chain step: V_M from `data` without any W_m in memory.

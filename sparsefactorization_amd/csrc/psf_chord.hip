@@ -971,6 +971,7 @@ const char* psf_build_info(void) {
          " | mixer: W_m computed inside the chain step (per-step kernels; one LDS-resident launch for short sequences)"
          " | bf16 chord path: f32 accumulation, one rounding per element; fwd: generic + LDS-window<bf16, TG<=16, NT=256, R=2>; bwd: fused dV+dW step<bf16, TG<=16, NT=256> (aligned full tiles), LDS-window dV<R=2> / dW<R=1><bf16, TG<=16> + generic;"
          " backward chain issued by the library (per-step launches)"
+         " | bf16 producers: fused MLP fwd<bf16> (one MFMA term, hidden layer in registers, E <= 64, inference)"
          " | arithmetic of the chord path: uncontracted mul+add (bf16: exact products fused), links ascending"
 #ifdef PSF_CSRC_HASH
          " | csrc=" PSF_CSRC_HASH  // build.csrc_hash() of the sources this library was built from (_lib.load compares)
