@@ -65,7 +65,7 @@ def run_size(name, rounds, iters):
         return s.elapsed_time(e) * 1e3 / iters
 
     with torch.no_grad():
-        assert fused_mlp.bf16_eligible(x, blocks) and fused_mlp.stackable(x, blocks)
+        assert fused_mlp.route(x, blocks) == "bf16_forward" and fused_mlp.stackable(x, blocks)  # (both would take it)
         a, b = routes["stacked"](x, blocks), routes["fused"](x, blocks)
         torch.cuda.synchronize()
         differ = sum(int((p != q).sum()) for p, q in zip(a, b))

@@ -8,7 +8,6 @@ produces the W_m (fused_mlp.py) and runs the chain (chord.chord_chain).
 from __future__ import annotations
 
 import ctypes
-import threading
 from typing import Sequence
 
 import torch
@@ -114,17 +113,6 @@ def _block_sizes(E: int, g: nn.Module, fs: Sequence[nn.Module]):
     return None if found is None else found[0]
 
 
-def _key(E: int, g: nn.Module, fs: Sequence[nn.Module]):
-    return (E, id(g), tuple(map(id, fs)))
-
-
-# What a successful eligibility check found, for the mixer_forward_in that follows it at once ON THE SAME THREAD (a third
-# fewer Python calls per no-grad forward of an LRA network): (key, sizes, pairs). Thread-local — two threads serving two models
-# never see each other's layer pairs — set only when the check says yes, consumed (and cleared) by the next forward, so it
-# keeps no module alive beyond that.
-_handoff = threading.local()
-
-
 def _route_ok(N: int, E: int, M: int, C: int, L: int, h, tokens: int = 1 << 62) -> bool:
     if route != "auto":
         return route == "always"
@@ -146,35 +134,36 @@ def _route_ok(N: int, E: int, M: int, C: int, L: int, h, tokens: int = 1 << 62) 
     return False
 
 
-def eligible_recipe(r: Recipe, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
-    """The fused mixer can run from this recipe, nothing needs a gradient, and ``route`` wants it."""
+def find(r: Recipe, g: nn.Module, fs: Sequence[nn.Module]):
+    """((M, h table, C, L), [(lin1, lin2), ...]) when the fused mixer can run from this recipe, nothing needs a gradient and
+    ``route`` wants it; None otherwise. ``mixer_forward_in`` takes it as ``found`` and does not walk the blocks again."""
     if not enabled or not r.ok() or torch.is_grad_enabled() and any(t.requires_grad for t in r.tensors() if t.is_floating_point()):
-        return False
+        return None
     if _needs_grad(torch.empty(0), [g, *fs]):
-        return False
-    _handoff.pending = None
+        return None
     found = _block_pairs(r.E, g, fs)
     if found is None:
-        return False
-    (M, h, C, L), pairs = found
-    ok = _route_ok(r.N, r.E, M, C, L, h, r.B * r.N) and _lib.load().psf_mixer_fwd_workspace(r.N, r.E, M, h, C, L) >= 0
-    if ok:
-        _handoff.pending = (_key(r.E, g, fs), found[0], pairs)
-    return ok
+        return None
+    M, h, C, L = found[0]
+    if _route_ok(r.N, r.E, M, C, L, h, r.B * r.N) and _lib.load().psf_mixer_fwd_workspace(r.N, r.E, M, h, C, L) >= 0:
+        return found
+    return None
 
 
-def mixer_forward_in(r: Recipe, g: nn.Module, fs: Sequence[nn.Module], use_residual: bool) -> torch.Tensor:
-    """V_M [B, N, C] from the recipe of ``data``. Caller checks ``eligible_recipe`` (or ``covered``) first."""
-    pend = getattr(_handoff, "pending", None)
-    _handoff.pending = None
-    if pend is not None and pend[0] == _key(r.E, g, fs):  # straight after this thread's eligibility check of the same blocks
-        (M, h, C, L), pairs = pend[1], pend[2]
-    else:
+def eligible_recipe(r: Recipe, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
+    """The fused mixer can run from this recipe, nothing needs a gradient, and ``route`` wants it."""
+    return find(r, g, fs) is not None
+
+
+def mixer_forward_in(r: Recipe, g: nn.Module, fs: Sequence[nn.Module], use_residual: bool, found=None) -> torch.Tensor:
+    """V_M [B, N, C] from the recipe of ``data``. ``found``: what ``find`` returned for these arguments; without it the caller
+    checks ``eligible_recipe`` (or ``covered``) first."""
+    if found is None:
         found = _block_pairs(r.E, g, fs)
         if found is None:
             raise ValueError("psf_mixer_fwd does not cover these blocks: every block must be Linear(E, h) -> GELU(erf) -> "
                              "Linear(h, out) in f32 on input width E, the link MLPs agreeing on L (check eligible() / covered())")
-        (M, h, C, L), pairs = found
+    (M, h, C, L), pairs = found
     B, N, E = r.B, r.N, r.E
     dev = r.src.device
     lib = _lib.load()

@@ -1,33 +1,15 @@
 """Fused PSFNet producer MLPs (``g`` and ``fs[0..M)``) — forward and backward in one launch each.
 
 ``MLPBlock`` is ``Linear(E, h) -> GELU -> Linear(h, out)`` (SyntheticExperiments/psf.py:35-60); PSFNet applies
-M+1 of them to the same ``data`` (psf.py:165,175).
-
-* ``psf_mlp_fwd_f32`` (csrc/mlp_fwd.hip) evaluates all of them from one read of ``data`` on the f32 matrix
-  core, the hidden layer staying in registers.
-* ``psf_mlp_bwd_f32`` (csrc/mlp_bwd.hip) is their backward: the hidden layer is recomputed, dX is accumulated
-  over all MLPs in registers, weight gradients are reduced in a fixed order. The forward therefore saves only
-  ``data`` and the parameters (autograd through the PyTorch layers keeps 2 x [T, (M+1) h] activations).
-
-``eligible`` (no gradient needed) / ``trainable`` (gradient needed) say whether a call can take these kernels;
-MLPs of another form, fp64, E > 64 (E > 32 when training), h > 128, out > 32 or CPU tensors use the stock modules.
-
-``bf16_eligible`` / ``fused_mlp_forward_bf16`` (csrc/mlp_fwd_bf16.hip, ``psf_mlp_fwd_bf16``) are the inference route of a bf16
-model (``PSFNet(...).to(torch.bfloat16)`` under ``no_grad``): one launch, one MFMA term per product, the three roundings of
-the layer-by-layer evaluation. Training in bf16, autocast with f32 parameters and the LRA widths keep ``stacked_apply``.
-
-``wide_ok`` / ``wide_apply`` (csrc/mlp_wide.hip) cover the LRA widths — E up to 1024, outputs up to 128; the reference
-ListOps network has E = 512, out = 12 and 128 (LRA/psf_training_config.py:2-30): the M+1 first layers are ONE stacked GEMM
-on the bf16 matrix pipe at f32 accuracy, forward, input gradient and weight gradient; the forward keeps the hidden
-pre-activations for the backward instead of recomputing them.
-
-``stackable`` / ``stacked_apply`` cover whatever is left (fp64, odd widths) with library GEMMs laid out for them: the M+1 first layers share their input, so they run as ONE Linear(E, sum h) — one GEMM
-forward, one GEMM for the input gradient (K = sum h, instead of M+1 GEMMs plus M accumulations of a [T, E]
-tensor) and one for the weight gradient; GELU and its backward are one kernel each.
+M+1 of them to the same ``data`` (psf.py:165,175). ``ROUTES`` is the ordered table of the ways to run them, each a predicate
+and the function it guards; ``route(x, blocks)`` names the first whose predicate takes a call and ``apply(x, blocks)`` runs it.
+The order is stated there and nowhere else. A call that no route takes (CPU tensors, MLPs of another form, a single fp64 MLP)
+gets None and runs the stock modules. ``_walk`` is the one check of a call against a route's limits (``_Limits``).
 """
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from typing import List, Optional, Sequence
 
 import torch
@@ -36,11 +18,51 @@ from torch import nn
 
 from . import _lib
 
-MAX_E, MAX_E_TRAIN, MAX_H, MAX_O, MAX_K = 64, 32, 128, 32, 32
-enabled = True        # module-level switches (tests / A-B timing)
+enabled = True        # module-level switches (tests / A-B timing), read at every call
 train_enabled = True
+wide_enabled = True
+bf16_enabled = True
 
-_vp = ctypes.c_void_p
+#: name: (predicate, function), in the order ``route`` asks the predicates; ``apply`` calls ``function(x, blocks)`` of the first
+#: that says yes. Names, not functions: both are looked up in this module when a call is routed, so a test or an A-B script
+#: that replaces ``wide_apply`` is the one that runs.
+ROUTES = {
+    # The narrow kernels. psf_mlp_fwd_f32 (csrc/mlp_fwd.hip) evaluates all MLPs from one read of ``data`` on the f32 matrix
+    # core, the hidden layer staying in registers. First: nothing needs a gradient, nothing is saved.
+    "narrow_forward": ("eligible", "fused_mlp_forward"),
+    # ... under autograd. psf_mlp_bwd_f32 (csrc/mlp_bwd.hip) recomputes the hidden layer, accumulates dX over all MLPs in
+    # registers and reduces weight gradients in a fixed order, so the forward saves only ``data`` and the parameters (autograd
+    # through the PyTorch layers keeps 2 x [T, (M+1) h] activations). Before the wide kernels, whose limits overlap these at
+    # E = 16 and 32: the narrow ones never let a hidden activation reach memory.
+    "narrow_train": ("trainable", "fused_mlp_apply"),
+    # f32 past the narrow limits: the LRA widths, E up to 1024, outputs up to 128 (the reference ListOps network has E = 512,
+    # out = 12 and 128, LRA/psf_training_config.py:2-30), with or without autograd (csrc/mlp_wide.hip). The M+1 first layers are
+    # ONE stacked GEMM on the bf16 matrix pipe at f32 accuracy, forward, input gradient and weight gradient; the forward keeps
+    # the hidden pre-activations for the backward instead of recomputing them.
+    "wide": ("wide_ok", "wide_apply"),
+    # Inference of a bf16 model (``PSFNet(...).to(torch.bfloat16)`` under ``no_grad``; csrc/mlp_fwd_bf16.hip): one launch, one
+    # MFMA term per product, the three roundings of the layer-by-layer evaluation. It shares no call with the three above
+    # (they want f32) and comes before the stacked route, which takes every dtype, at every T: 3.3-5.7 x faster than
+    # stacked_apply at every size of profiles/bf16_mlp_ab.md (1 024 tokens: 398.9 -> 109.8 us per call; 1 048 576 tokens:
+    # 1947.7 -> 342.9 us). Training in bf16, autocast with f32 parameters and the LRA widths in bf16 go on to ``stacked_apply``.
+    "bf16_forward": ("bf16_eligible", "fused_mlp_forward_bf16"),
+    # Last, whatever no kernel of ours took (fp64, odd widths), on library GEMMs laid out for it: the M+1 first layers share
+    # their input, so they run as ONE Linear(E, sum h) — one GEMM forward, one for the input gradient (K = sum h, instead of
+    # M+1 GEMMs plus M accumulations of a [T, E] tensor) and one for the weight gradient; GELU and its backward one kernel each.
+    "stacked": ("stackable", "stacked_apply"),
+}
+
+#: What a kernel family takes: x and the parameters of ``dtype``, E within [e_min, e_max] and a multiple of e_mult (bf16: a
+#: row of X is then a whole number of 16-byte vectors), hidden widths <= h_max, output widths <= o_max, at most k_max MLPs
+#: (the narrow forward launchers split a longer call). ``all_params``: the dtype of all four parameters of a block is looked
+#: at, not only the first layer's weight. ``_ANY`` is ``stackable``'s looser rule: the dtype of x, whatever it is, at any size.
+_Limits = namedtuple("_Limits", "dtype e_min e_max e_mult h_max o_max k_max all_params")
+MAX_K = 32            # MLPs per launch of the narrow kernels
+_NARROW = _Limits(torch.float32, 4, 64, 4, 128, 32, 1 << 30, False)
+_NARROW_TRAIN = _NARROW._replace(e_max=32, k_max=MAX_K)
+_BF16 = _Limits(torch.bfloat16, 8, 64, 8, 128, 32, 1 << 30, True)
+_WIDE = _Limits(torch.float32, 16, 1024, 16, 128, 128, 24, False)
+_ANY = _Limits(None, 0, 1 << 30, 1, 1 << 30, 1 << 30, 1 << 30, False)
 
 
 def _two_layer(block: nn.Module) -> Optional[tuple]:
@@ -74,58 +96,108 @@ def _needs_grad(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
     return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for b in blocks for p in b.parameters()))
 
 
-def _shapes_ok(x: torch.Tensor, blocks: Sequence[nn.Module], max_e: int) -> bool:
-    if not x.is_cuda or x.dtype != torch.float32 or x.dim() < 2 or not len(blocks):
-        return False
+def _walk(x: torch.Tensor, blocks: Sequence[nn.Module], lim: _Limits) -> Optional[list]:
+    """The one block walk of every predicate: [(lin1, lin2), ...] when ``x`` is a HIP tensor [..., E], every block a two-layer
+    erf-GELU MLP on input width E and the call is not empty and inside ``lim``; None otherwise."""
+    dtype, e_min, e_max, e_mult, h_max, o_max, k_max, all_params = lim
+    if not x.is_cuda or x.dim() < 2 or x.dtype != (dtype or x.dtype) or not 1 <= len(blocks) <= k_max:
+        return None
     E = x.shape[-1]
-    if E < 4 or E > max_e or E % 4:
-        return False
+    if E < e_min or E > e_max or E % e_mult:
+        return None
+    pairs = []
     for b in blocks:
-        pair = _two_layer(b)
-        if pair is None:
-            return False
-        l1, l2 = pair
-        if l1.in_features != E or l1.out_features > MAX_H or l2.out_features > MAX_O or l1.weight.dtype != torch.float32:
-            return False
-    return True
+        l1, l2 = _two_layer(b) or (None, None)
+        if l1 is None or l1.in_features != E or l1.out_features > h_max or l2.out_features > o_max or l1.weight.dtype != x.dtype:
+            return None
+        if all_params and any(p.dtype != dtype for p in (l1.bias, l2.weight, l2.bias)):
+            return None
+        pairs.append((l1, l2))
+    return pairs
 
 
 def eligible(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
     """Inference: the fused forward can replace ``[b(x) for b in blocks]`` and nothing needs a gradient."""
-    return enabled and not _needs_grad(x, blocks) and _shapes_ok(x, blocks, MAX_E)
+    return enabled and not _needs_grad(x, blocks) and _walk(x, blocks, _NARROW) is not None
 
 
 def trainable(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
     """Training: fused forward + fused backward (``fused_mlp_apply``) can replace the PyTorch layers."""
-    return enabled and train_enabled and _needs_grad(x, blocks) and len(blocks) <= MAX_K and _shapes_ok(x, blocks, MAX_E_TRAIN)
+    return enabled and train_enabled and _needs_grad(x, blocks) and _walk(x, blocks, _NARROW_TRAIN) is not None
+
+
+def bf16_eligible(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
+    """Inference in bf16: ``fused_mlp_forward_bf16`` can replace ``[b(x) for b in blocks]`` — a HIP bf16 input, two-layer
+    erf-GELU blocks whose four parameters all are bf16, sizes within psf_mlp_fwd_bf16's limits, nothing needing a gradient."""
+    return enabled and bf16_enabled and not _needs_grad(x, blocks) and _walk(x, blocks, _BF16) is not None
+
+
+def wide_ok(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
+    """The wide kernels (psf_mlp_wide_*) can replace ``[b(x) for b in blocks]``, with or without autograd."""
+    pairs = _walk(x, blocks, _WIDE) if enabled and wide_enabled else None
+    if pairs is None:
+        return False
+    E = x.shape[-1]
+    J = sum((l1.out_features + 31) // 32 * 32 for l1, _ in pairs)
+    return x.numel() // E * max(E, J) < 2 ** 30  # 32-bit lane offsets into a bf16 plane
+
+
+def stackable(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
+    """GPU call of >= 2 two-layer MLPs that share their input and that the fused kernels do not take, of any width."""
+    return enabled and len(blocks) >= 2 and _walk(x, blocks, _ANY) is not None
+
+
+def route(x: torch.Tensor, blocks: Sequence[nn.Module]) -> Optional[str]:
+    """The name of the first of ``ROUTES`` that takes ``[b(x) for b in blocks]``, or None."""
+    here = globals()
+    return next((name for name, (predicate, _fn) in ROUTES.items() if here[predicate](x, blocks)), None)
+
+
+def apply(x: torch.Tensor, blocks: Sequence[nn.Module]) -> Optional[List[torch.Tensor]]:
+    """``[b(x) for b in blocks]`` by that route; None when no route takes the call (the caller then runs the modules)."""
+    name = route(x, blocks)
+    return None if name is None else globals()[ROUTES[name][1]](x, blocks)
 
 
 def _ptrs(tensors: Sequence[torch.Tensor]):
-    return (_vp * len(tensors))(*[t.data_ptr() for t in tensors])
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _sizes(params: Sequence[torch.Tensor]):
+    """(K, h table, O table) of params = (A0, a0, B0, b0, A1, ...)."""
+    K = len(params) // 4
+    return K, (ctypes.c_int32 * K)(*[A.shape[0] for A in params[0::4]]), (ctypes.c_int32 * K)(*[B.shape[0] for B in params[2::4]])
+
+
+def _scratch(nbytes: int, dev) -> torch.Tensor:
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)  # the caching allocator aligns to 512 bytes
+
+
+def _bytes(kernel: str, entry: str, *args) -> int:
+    """What the library's ``entry(*args)`` asks for ``kernel``; sizes outside the kernel's limits raise."""
+    nbytes = getattr(_lib.load(), entry)(*args)
+    if nbytes < 0:
+        raise ValueError(f"{kernel} does not support these layer sizes")
+    return nbytes
 
 
 def _forward_raw(x2: torch.Tensor, params: Sequence[torch.Tensor]) -> List[torch.Tensor]:
-    """x2 [T, E] contiguous; params = (A0, a0, B0, b0, A1, ...) contiguous fp32. One launch per <= MAX_K MLPs."""
+    """x2 [T, E] contiguous, f32 or bf16; params = (A0, a0, B0, b0, A1, ...) contiguous of x2's dtype. One launch per <= MAX_K
+    MLPs: psf_mlp_fwd_f32 or psf_mlp_fwd_bf16, which take the same arguments."""
     T, E = x2.shape
     dev = x2.device
-    lib = _lib.load()
+    kernel, entry = ("psf_mlp_fwd_bf16",) * 2 if x2.dtype == torch.bfloat16 else ("psf_mlp_fwd", "psf_mlp_fwd_f32")
+    launch = getattr(_lib.load(), entry)
     outs: List[torch.Tensor] = []
-    n_mlp = len(params) // 4
-    for start in range(0, n_mlp, MAX_K):
-        grp = params[4 * start:4 * min(start + MAX_K, n_mlp)]
-        K = len(grp) // 4
-        As, as_, Bs, bs = grp[0::4], grp[1::4], grp[2::4], grp[3::4]
-        ys = [torch.empty((T, B.shape[0]), dtype=torch.float32, device=dev) for B in Bs]
-        h = (ctypes.c_int32 * K)(*[A.shape[0] for A in As])
-        O = (ctypes.c_int32 * K)(*[B.shape[0] for B in Bs])
-        ws_bytes = lib.psf_mlp_fwd_workspace(E, K, h, O)
-        if ws_bytes < 0:
-            raise ValueError("psf_mlp_fwd does not support these layer sizes")
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)  # packed weight images
+    for start in range(0, len(params), 4 * MAX_K):
+        grp = params[start:start + 4 * MAX_K]
+        K, h, O = _sizes(grp)
+        ys = [torch.empty((T, B.shape[0]), dtype=x2.dtype, device=dev) for B in grp[2::4]]
+        ws = _scratch(_bytes(kernel, kernel + "_workspace", E, K, h, O), dev)  # packed weight images
         with torch.cuda.device(dev):
-            rc = lib.psf_mlp_fwd_f32(x2.data_ptr(), T, E, K, _ptrs(As), _ptrs(as_), _ptrs(Bs), _ptrs(bs), h, O, _ptrs(ys),
-                                     ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-        _lib.check(rc, "psf_mlp_fwd_f32")
+            rc = launch(x2.data_ptr(), T, E, K, _ptrs(grp[0::4]), _ptrs(grp[1::4]), _ptrs(grp[2::4]), _ptrs(grp[3::4]), h, O,
+                        _ptrs(ys), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, entry)
         outs.extend(ys)
     return outs
 
@@ -133,22 +205,15 @@ def _forward_raw(x2: torch.Tensor, params: Sequence[torch.Tensor]) -> List[torch
 def _backward_raw(x2: torch.Tensor, params: Sequence[torch.Tensor], gys: Sequence[torch.Tensor], need_dx: bool):
     T, E = x2.shape
     dev = x2.device
-    lib = _lib.load()
-    K = len(params) // 4
-    As, as_, Bs = params[0::4], params[1::4], params[2::4]
-    h = (ctypes.c_int32 * K)(*[A.shape[0] for A in As])
-    O = (ctypes.c_int32 * K)(*[B.shape[0] for B in Bs])
+    K, h, O = _sizes(params)
     grads = [torch.empty_like(p) for p in params]
     dX = torch.empty_like(x2) if need_dx else None
-    ws_bytes = lib.psf_mlp_bwd_workspace(T, E, K, h, O)
-    if ws_bytes < 0:
-        raise ValueError("psf_mlp_bwd does not support these layer sizes")
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)  # packed weights + per-wave partial sums
+    ws = _scratch(_bytes("psf_mlp_bwd", "psf_mlp_bwd_workspace", T, E, K, h, O), dev)  # packed weights + per-wave partial sums
     with torch.cuda.device(dev):
-        rc = lib.psf_mlp_bwd_f32(x2.data_ptr(), T, E, K, _ptrs(As), _ptrs(as_), _ptrs(Bs), h, O, _ptrs(gys),
-                                 dX.data_ptr() if need_dx else None, _ptrs(grads[0::4]), _ptrs(grads[1::4]),
-                                 _ptrs(grads[2::4]), _ptrs(grads[3::4]), ws.data_ptr(), ws_bytes,
-                                 _lib.stream_ptr(dev))
+        rc = _lib.load().psf_mlp_bwd_f32(x2.data_ptr(), T, E, K, _ptrs(params[0::4]), _ptrs(params[1::4]), _ptrs(params[2::4]),
+                                         h, O, _ptrs(gys), dX.data_ptr() if need_dx else None, _ptrs(grads[0::4]),
+                                         _ptrs(grads[1::4]), _ptrs(grads[2::4]), _ptrs(grads[3::4]), ws.data_ptr(), ws.numel(),
+                                         _lib.stream_ptr(dev))
     _lib.check(rc, "psf_mlp_bwd_f32")
     return dX, grads
 
@@ -198,7 +263,7 @@ def _params_of(blocks: Sequence[nn.Module]) -> List[torch.Tensor]:
 
 
 def fused_mlp_forward(x: torch.Tensor, blocks: Sequence[nn.Module]) -> List[torch.Tensor]:
-    """[block(x) for block in blocks] without autograd, by the fused kernel. Caller checks ``eligible`` first."""
+    """[block(x) for block in blocks] without autograd, by the fused kernel (f32 or bf16, by x's dtype). Caller checks ``eligible`` first."""
     lead, E = x.shape[:-1], x.shape[-1]
     x2 = x.detach().reshape(-1, E).contiguous()
     params = [p.detach().contiguous() for p in _params_of(blocks)]
@@ -213,144 +278,38 @@ def fused_mlp_apply(x: torch.Tensor, blocks: Sequence[nn.Module]) -> List[torch.
     return [y.reshape(*lead, y.shape[1]) for y in ys]
 
 
-bf16_enabled = True   # the fused bf16 forward (psf_mlp_fwd_bf16) for bf16 models under no_grad
-# No threshold on T: the fused route measured 3.3-5.7 x faster than stacked_apply at every size of profiles/bf16_mlp_ab.md
-# (1 024 tokens: 398.9 -> 109.8 us per call; 1 048 576 tokens: 1947.7 -> 342.9 us).
-BF16_MIN_E = 8        # E a multiple of 8: an X row is then a whole number of 16-byte vectors
-
-
-def bf16_eligible(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
-    """Inference in bf16: ``fused_mlp_forward_bf16`` can replace ``[b(x) for b in blocks]`` — a HIP bf16 input, two-layer
-    erf-GELU blocks whose four parameters all are bf16, sizes within psf_mlp_fwd_bf16's limits, nothing needing a gradient."""
-    if not (enabled and bf16_enabled) or _needs_grad(x, blocks):
-        return False
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() < 2 or not len(blocks):
-        return False
-    E = x.shape[-1]
-    if E < BF16_MIN_E or E > MAX_E or E % 8:
-        return False
-    for b in blocks:
-        pair = _two_layer(b)
-        if pair is None:
-            return False
-        l1, l2 = pair
-        if l1.in_features != E or l1.out_features > MAX_H or l2.out_features > MAX_O:
-            return False
-        if any(p.dtype != torch.bfloat16 for p in (l1.weight, l1.bias, l2.weight, l2.bias)):
-            return False
-    return True
-
-
-def _forward_raw_bf16(x2: torch.Tensor, params: Sequence[torch.Tensor]) -> List[torch.Tensor]:
-    """x2 [T, E] contiguous bf16; params = (A0, a0, B0, b0, A1, ...) contiguous bf16. One launch per <= MAX_K MLPs."""
-    T, E = x2.shape
-    dev = x2.device
-    lib = _lib.load()
-    outs: List[torch.Tensor] = []
-    n_mlp = len(params) // 4
-    for start in range(0, n_mlp, MAX_K):
-        grp = params[4 * start:4 * min(start + MAX_K, n_mlp)]
-        K = len(grp) // 4
-        As, as_, Bs, bs = grp[0::4], grp[1::4], grp[2::4], grp[3::4]
-        ys = [torch.empty((T, B.shape[0]), dtype=torch.bfloat16, device=dev) for B in Bs]
-        h = (ctypes.c_int32 * K)(*[A.shape[0] for A in As])
-        O = (ctypes.c_int32 * K)(*[B.shape[0] for B in Bs])
-        ws_bytes = lib.psf_mlp_fwd_bf16_workspace(E, K, h, O)
-        if ws_bytes < 0:
-            raise ValueError("psf_mlp_fwd_bf16 does not support these layer sizes")
-        ws = _scratch(ws_bytes, dev)  # packed weight images
-        with torch.cuda.device(dev):
-            rc = lib.psf_mlp_fwd_bf16(x2.data_ptr(), T, E, K, _ptrs(As), _ptrs(as_), _ptrs(Bs), _ptrs(bs), h, O, _ptrs(ys),
-                                      ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-        _lib.check(rc, "psf_mlp_fwd_bf16")
-        outs.extend(ys)
-    return outs
-
-
-def fused_mlp_forward_bf16(x: torch.Tensor, blocks: Sequence[nn.Module]) -> List[torch.Tensor]:
-    """[block(x) for block in blocks] of a bf16 model without autograd, by the fused bf16 kernel: the three roundings of the
-    layer-by-layer evaluation, the hidden layer never in memory. Caller checks ``bf16_eligible`` first."""
-    lead, E = x.shape[:-1], x.shape[-1]
-    x2 = x.detach().reshape(-1, E).contiguous()
-    params = [p.detach().contiguous() for p in _params_of(blocks)]
-    return [y.reshape(*lead, y.shape[1]) for y in _forward_raw_bf16(x2, params)]
-
-
-WIDE_MAX_E, WIDE_MAX_O, WIDE_MAX_K = 1024, 128, 24
-wide_enabled = True
-
-
-def wide_ok(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
-    """The wide kernels (psf_mlp_wide_*) can replace ``[b(x) for b in blocks]``, with or without autograd. Callers try
-    ``eligible`` / ``trainable`` (the narrow kernels, which never let a hidden activation reach memory) first."""
-    if not (enabled and wide_enabled) or not x.is_cuda or x.dtype != torch.float32 or x.dim() < 2 or not 1 <= len(blocks) <= WIDE_MAX_K:
-        return False
-    E = x.shape[-1]
-    if E < 16 or E > WIDE_MAX_E or E % 16:
-        return False
-    J = 0
-    for b in blocks:
-        pair = _two_layer(b)
-        if pair is None:
-            return False
-        l1, l2 = pair
-        if l1.in_features != E or l1.out_features > MAX_H or l2.out_features > WIDE_MAX_O or l1.weight.dtype != torch.float32:
-            return False
-        J += (l1.out_features + 31) // 32 * 32
-    T = x.numel() // E
-    return T * max(E, J) < 2 ** 30  # 32-bit lane offsets into a bf16 plane
-
-
-def _wide_sizes(x2: torch.Tensor, params: Sequence[torch.Tensor]):
-    K = len(params) // 4
-    h = (ctypes.c_int32 * K)(*[A.shape[0] for A in params[0::4]])
-    O = (ctypes.c_int32 * K)(*[B.shape[0] for B in params[2::4]])
-    return x2.shape[0], x2.shape[1], K, h, O
-
-
-def _scratch(nbytes: int, dev) -> torch.Tensor:
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)  # the caching allocator aligns to 512 bytes
+fused_mlp_forward_bf16 = fused_mlp_forward  # of a bf16 model: the fused bf16 kernel. Caller checks ``bf16_eligible`` first.
 
 
 def _wide_forward_raw(x2: torch.Tensor, params: Sequence[torch.Tensor], keep: bool = True):
     """(Y_0..Y_{K-1}, saved): ``saved`` holds X as bf16 term planes and the hidden pre-activations (mlp_wide.hip).
     ``keep`` False (inference): no record is kept — the library works in scratch and skips what only a backward reads."""
-    T, E, K, h, O = _wide_sizes(x2, params)
+    T, E = x2.shape
     dev = x2.device
-    lib = _lib.load()
-    As, as_, Bs, bs = params[0::4], params[1::4], params[2::4], params[3::4]
-    n_saved, n_ws = lib.psf_mlp_wide_saved_bytes(T, E, K, h, O), lib.psf_mlp_wide_fwd_workspace(T, E, K, h, O)
-    if n_saved < 0 or n_ws < 0:
-        raise ValueError("psf_mlp_wide_fwd does not support these layer sizes")
+    K, h, O = _sizes(params)
+    n_saved = _bytes("psf_mlp_wide_fwd", "psf_mlp_wide_saved_bytes", T, E, K, h, O)
     saved = _scratch(n_saved, dev) if keep else None
-    ws = _scratch(n_ws + (0 if keep else n_saved + 256), dev)
-    ys = [torch.empty((T, B.shape[0]), dtype=torch.float32, device=dev) for B in Bs]
+    ws = _scratch(_bytes("psf_mlp_wide_fwd", "psf_mlp_wide_fwd_workspace", T, E, K, h, O) + (0 if keep else n_saved + 256), dev)
+    ys = [torch.empty((T, B.shape[0]), dtype=torch.float32, device=dev) for B in params[2::4]]
     with torch.cuda.device(dev):
-        rc = lib.psf_mlp_wide_fwd_f32(x2.data_ptr(), T, E, K, _ptrs(As), _ptrs(as_), _ptrs(Bs), _ptrs(bs), h, O, _ptrs(ys),
-                                      saved.data_ptr() if keep else None, saved.numel() if keep else 0, ws.data_ptr(), ws.numel(),
-                                      _lib.stream_ptr(dev))
+        rc = _lib.load().psf_mlp_wide_fwd_f32(x2.data_ptr(), T, E, K, _ptrs(params[0::4]), _ptrs(params[1::4]), _ptrs(params[2::4]),
+                                              _ptrs(params[3::4]), h, O, _ptrs(ys), saved.data_ptr() if keep else None,
+                                              saved.numel() if keep else 0, ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
     _lib.check(rc, "psf_mlp_wide_fwd_f32")
     return ys, saved
 
 
 def _wide_backward_raw(saved: torch.Tensor, T: int, E: int, params: Sequence[torch.Tensor], gys: Sequence[torch.Tensor], need_dx: bool):
     dev = saved.device
-    lib = _lib.load()
-    K = len(params) // 4
-    As, Bs = params[0::4], params[2::4]
-    h = (ctypes.c_int32 * K)(*[A.shape[0] for A in As])
-    O = (ctypes.c_int32 * K)(*[B.shape[0] for B in Bs])
+    K, h, O = _sizes(params)
     grads = [torch.empty_like(p) for p in params]
     dX = torch.empty((T, E), dtype=torch.float32, device=dev) if need_dx else None
-    n_ws = lib.psf_mlp_wide_bwd_workspace(T, E, K, h, O)
-    if n_ws < 0:
-        raise ValueError("psf_mlp_wide_bwd does not support these layer sizes")
-    ws = _scratch(n_ws, dev)
+    ws = _scratch(_bytes("psf_mlp_wide_bwd", "psf_mlp_wide_bwd_workspace", T, E, K, h, O), dev)
     with torch.cuda.device(dev):
-        rc = lib.psf_mlp_wide_bwd_f32(saved.data_ptr(), saved.numel(), T, E, K, _ptrs(As), _ptrs(Bs), h, O, _ptrs(gys),
-                                      dX.data_ptr() if need_dx else None, _ptrs(grads[0::4]), _ptrs(grads[1::4]),
-                                      _ptrs(grads[2::4]), _ptrs(grads[3::4]), ws.data_ptr(), ws.numel(),
-                                      _lib.stream_ptr(dev))
+        rc = _lib.load().psf_mlp_wide_bwd_f32(saved.data_ptr(), saved.numel(), T, E, K, _ptrs(params[0::4]), _ptrs(params[2::4]), h, O,
+                                              _ptrs(gys), dX.data_ptr() if need_dx else None, _ptrs(grads[0::4]), _ptrs(grads[1::4]),
+                                              _ptrs(grads[2::4]), _ptrs(grads[3::4]), ws.data_ptr(), ws.numel(),
+                                              _lib.stream_ptr(dev))
     _lib.check(rc, "psf_mlp_wide_bwd_f32")
     return dX, grads
 
@@ -384,14 +343,6 @@ def wide_apply(x: torch.Tensor, blocks: Sequence[nn.Module]) -> List[torch.Tenso
     else:
         ys, _ = _wide_forward_raw(x.detach().reshape(-1, E).contiguous(), [p.detach().contiguous() for p in _params_of(blocks)], keep=False)
     return [y.reshape(*lead, y.shape[1]) for y in ys]
-
-
-def stackable(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
-    """GPU call of >= 2 two-layer MLPs that share their input and that the fused kernels do not take."""
-    if not enabled or not x.is_cuda or len(blocks) < 2 or x.dim() < 2:
-        return False
-    pairs = [_two_layer(b) for b in blocks]
-    return all(p is not None and p[0].in_features == x.shape[-1] and p[0].weight.dtype == x.dtype for p in pairs)
 
 
 def stacked_apply(x: torch.Tensor, blocks: Sequence[nn.Module]) -> List[torch.Tensor]:

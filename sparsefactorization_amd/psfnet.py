@@ -166,57 +166,35 @@ class _ChordMixer(nn.Module):
     def link_weights(self, data: torch.Tensor) -> List[torch.Tensor]:
         """W_m = fs[m](data), each [B, N, L] (psf.py:175)."""
         fs = list(self.fs)
-        if fused_mlp.eligible(data, fs):
-            return fused_mlp.fused_mlp_forward(data, fs)
-        if fused_mlp.trainable(data, fs):
-            return fused_mlp.fused_mlp_apply(data, fs)
-        if fused_mlp.wide_ok(data, fs):
-            return fused_mlp.wide_apply(data, fs)
-        if fused_mlp.bf16_eligible(data, fs):
-            return fused_mlp.fused_mlp_forward_bf16(data, fs)
-        if fused_mlp.stackable(data, fs):
-            return fused_mlp.stacked_apply(data, fs)
-        return [f(data) for f in fs]
+        outs = fused_mlp.apply(data, fs)
+        return [f(data) for f in fs] if outs is None else outs
 
     def produce(self, data: torch.Tensor):
         """(V, [W_m]) = (g(data), [fs[m](data)]) — psf.py:165,175. All M+1 MLPs run as ONE fused launch from one
-        read of ``data``, and under autograd their backward is one fused launch too (fused_mlp.py); shapes the
+        read of ``data``, and under autograd their backward is one fused launch too (fused_mlp.ROUTES); shapes the
         kernels do not cover use the PyTorch layers.
         Returns links = None when the chain is not fused (each W_m is then produced right before its step)."""
         if not self.fused_chain:
             return self.g(data), None
-        blocks = [self.g] + list(self.fs)
-        if fused_mlp.eligible(data, blocks):
-            outs = fused_mlp.fused_mlp_forward(data, blocks)
-            return outs[0], outs[1:]
-        if fused_mlp.trainable(data, blocks):
-            outs = fused_mlp.fused_mlp_apply(data, blocks)
-            return outs[0], outs[1:]
-        if fused_mlp.wide_ok(data, blocks):
-            outs = fused_mlp.wide_apply(data, blocks)
-            return outs[0], outs[1:]
-        if fused_mlp.bf16_eligible(data, blocks):
-            outs = fused_mlp.fused_mlp_forward_bf16(data, blocks)
-            return outs[0], outs[1:]
-        if fused_mlp.stackable(data, blocks):
-            outs = fused_mlp.stacked_apply(data, blocks)
-            return outs[0], outs[1:]
-        return self.g(data), self.link_weights(data)
+        outs = fused_mlp.apply(data, [self.g, *self.fs])
+        if outs is None:
+            return self.g(data), self.link_weights(data)
+        return outs[0], outs[1:]
 
     def mix_from_recipe(self, recipe, use_residuals: bool):
         """V_M from the RECIPE of ``data`` (fused_mixer.Recipe: the affine input layer or the embedding lookup that PSFNet
         applies first, psf.py:151-162): neither ``data`` nor any W_m is written to memory. None when that path does not apply."""
-        if recipe is not None and self.fused_chain and fused_mixer.eligible_recipe(recipe, self.g, list(self.fs)):
-            return fused_mixer.mixer_forward_in(recipe, self.g, list(self.fs), use_residuals)
-        return None
+        if recipe is None or not self.fused_chain:
+            return None
+        fs = list(self.fs)
+        found = fused_mixer.find(recipe, self.g, fs)
+        return None if found is None else fused_mixer.mixer_forward_in(recipe, self.g, fs, use_residuals, found)
 
     def mix_from_data(self, data: torch.Tensor, use_residuals: bool):
         """V_M straight from ``data`` with every W_m computed inside its chain step and never written (fused_mixer.py,
         csrc/fwd_mlp_step.h) — psf.py:165-188 in M + 2 launches. None when that path does not apply (a gradient is
         needed, shapes outside its limits): the caller then runs ``produce`` + ``mix``."""
-        if self.fused_chain and fused_mixer.eligible(data, self.g, list(self.fs)):
-            return fused_mixer.mixer_forward(data, self.g, list(self.fs), use_residuals)
-        return None
+        return None if data.requires_grad else self.mix_from_recipe(fused_mixer.Recipe.data(data), use_residuals)
 
     def mix(self, data: torch.Tensor, V: torch.Tensor, use_residuals: bool, links=None) -> torch.Tensor:
         """The hot loop of PSFNet.forward (SyntheticExperiments/psf.py:167-188). ``links`` may carry

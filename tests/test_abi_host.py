@@ -528,28 +528,49 @@ def test_library_carries_the_hash_of_its_sources_and_a_stale_one_is_reported(mon
         _lib._warn_if_stale(lib)
 
 
-def test_fused_mixer_handoff_is_per_thread_and_uncovered_blocks_raise():
-    """fused_mixer hands what its eligibility check found to the forward that follows (round 5: a third fewer Python calls).
-    That hand-off is per thread and keyed: another thread's check can never give this forward another model's layers, and
-    blocks the path does not cover raise a ValueError naming the requirement instead of a TypeError."""
+def test_fused_mixer_handoff_is_per_thread_and_uncovered_blocks_raise(lib, monkeypatch):
+    """fused_mixer hands what its eligibility check found to the forward that follows as an argument (``find`` ->
+    ``mixer_forward_in(..., found)``): the module keeps no state between the two calls, so two threads serving two models each
+    get their own layers back, and blocks the path does not cover raise a ValueError naming the requirement instead of a
+    TypeError."""
     import threading
     from sparsefactorization_amd import fused_mixer
     from sparsefactorization_amd.psfnet import MLPBlock
+    assert not any(hasattr(fused_mixer, name) for name in ("_handoff", "_key", "_pending", "threading"))
     g, fs = MLPBlock([32, 'GELU'], 32, 8), [MLPBlock([32, 'GELU'], 32, 12) for _ in range(3)]
     found = fused_mixer._block_pairs(32, g, fs)
     assert found is not None and found[0][0] == 3 and found[0][2:] == (8, 12) and len(found[1]) == 4
-    fused_mixer._handoff.pending = (fused_mixer._key(32, g, fs), found[0], found[1])
-    seen = []
-    t = threading.Thread(target=lambda: seen.append(getattr(fused_mixer._handoff, "pending", None)))
-    t.start()
-    t.join()
-    assert seen == [None]  # the other thread sees nothing of this thread's pending hand-off
-    fused_mixer._handoff.pending = None
+    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))  # everything but the device
+    monkeypatch.setattr(fused_mixer, "route", "always")
+    models = [(g, fs), (MLPBlock([16, 'GELU'], 32, 4), [MLPBlock([16, 'GELU'], 32, 9) for _ in range(2)])]
+    seen, barrier = {}, threading.Barrier(2, timeout=20)
+
+    def serve(i):
+        gi, fi = models[i]
+        with torch.no_grad():
+            r = fused_mixer.Recipe.data(torch.zeros(2, 64, 32))
+            assert fused_mixer.eligible_recipe(r, gi, fi)
+            barrier.wait()  # both threads have asked before either takes its answer
+            first = fused_mixer.find(r, gi, fi)
+            barrier.wait()
+            seen[i] = (first, fused_mixer.find(r, gi, fi))
+    threads = [threading.Thread(target=serve, args=(i,)) for i in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for i, (gi, fi) in enumerate(models):
+        for sizes, pairs in seen[i]:
+            assert (sizes[0], list(sizes[1]), sizes[2], sizes[3]) == ((3, [32] * 4, 8, 12), (2, [16] * 3, 4, 9))[i]
+            assert all(a is b for got, blk in zip(pairs, [gi, *fi]) for a, b in zip(got, (blk.network[0], blk.network[2])))
+    monkeypatch.setattr(fused_mixer, "route", "never")
+    with torch.no_grad():
+        assert fused_mixer.find(fused_mixer.Recipe.data(torch.zeros(2, 64, 32)), g, fs) is None
+    monkeypatch.undo()
     odd = [MLPBlock([32, 'GELU'], 32, 12), MLPBlock([32, 'GELU'], 32, 13)]  # link MLPs that disagree on L
     assert fused_mixer._block_pairs(32, g, odd) is None
     with pytest.raises(ValueError, match="does not cover these blocks"):
         fused_mixer.mixer_forward(torch.zeros(1, 64, 32), g, odd, True)
-    assert getattr(fused_mixer._handoff, "pending", None) is None
 
 
 def test_interleaved_fronts_visit_every_tile_once():
