@@ -162,7 +162,9 @@ int psf_chord_spmm_fwd_f64(const double* W, const double* V, const double* res, 
  *                 Backward chain: psf_chord_chain_bwd_bf16 issues the per-step launches and the one residual sum inside
  *                 the library (below).
  *                 Producer MLPs, forward (inference): psf_mlp_fwd_bf16 (below, next to psf_mlp_fwd_f32).
- * Not covered: float16, mixed dtypes, the bf16 mixer / flat-head entries, the bf16 producer backward, a one-launch bf16 backward chain, and
+ *                 Mixer of a short sequence in one launch (inference): psf_mixer_fwd_bf16 (below, next to psf_mixer_fwd_f32).
+ * Not covered: float16, mixed dtypes, the bf16 mixer with W computed inside per-step kernels (long sequences) or from an
+ *                 input recipe, the bf16 flat-head entry, the bf16 producer backward, a one-launch bf16 backward chain, and
  *                 an edge instance of the bf16 fused backward step (ragged N, other far offsets, W / dW off their 16-byte
  *                 boundary: those steps run the dW and dV window kernels).
  */
@@ -419,6 +421,36 @@ int psf_mixer_fwd_f32(const float* X, int64_t B, int64_t N, int32_t E, int32_t M
                       int64_t workspace_bytes, void* stream);
 
 /*
+ * The mixer of a SHORT sequence for a bf16 model (raw bits), in one launch plus the packing of the weights
+ * (csrc/mixer_lds_bf16.h): a workgroup owns a sequence, keeps its data rows in registers and its V in LDS as bf16 through
+ * all M steps, computes V0 = g(X) and every W_m = fs[m](X) on chip, and rounds each W_m to bf16 before the step reads it.
+ * THE RESULT IS THE BITS OF psf_mlp_fwd_bf16 FOLLOWED BY psf_chord_chain_fwd_bf16 on the same operands — V0 and every stored
+ * step, NaN and Inf included: the two kernels' arithmetic (three roundings per MLP; f32 accumulator, links ascending with
+ * the exact product fused, the residual added in f32, one rounding per step) is reused, not restated. What goes away is
+ * the M + 1 producer outputs in memory (2 M L bytes per token written and read back) and two of the three launches.
+ *   Tables as psf_mixer_fwd_f32: M + 1 entries, MLP 0 = g (E -> h[0] -> C), MLPs 1..M = fs[0..M) (E -> h[k] -> L); X [B,N,E].
+ *   V0 [B,N,C] receives g(X) and may be NULL (nothing is written then); out_steps as psf_chord_chain_fwd_bf16: M pointers
+ *   that may alternate two buffers, a buffer that a later step overwrites is not stored at all; the result is
+ *   out_steps[M-1]. Chord offsets only. There is no recipe input and no per-step form for longer sequences.
+ *   Limits: N a multiple of 32, 32 <= N <= 512; C = 8 or 16; E a multiple of 8, 8 <= E <= 64; 1 <= h[k] <= 128;
+ *   4 <= L <= 20; 1 <= M <= 31; 0 <= B < 2^31; X, V0 and every out_steps[m] 16-byte aligned, weights and biases 2-byte aligned.
+ *   psf_mixer_fwd_bf16_plan: 2 = the single launch runs, 0 = not covered (outside the limits, or knob "mixer_lds" = 0).
+ *   psf_mixer_fwd_bf16_workspace: bytes of 16-byte-aligned device scratch (6912 per 32 hidden rows of each MLP), or -1
+ *   outside the limits.
+ *   Validation, before any HIP call and in this order: NULL tables (PSF_E_NULL); B (PSF_E_SHAPE); a shape that
+ *   psf_mixer_fwd_bf16_plan answers 0 for, the knob included: PSF_E_UNSUPPORTED (not an error: the caller runs the two
+ *   entries above); X, V0 alignment (PSF_E_ALIGN); workspace too small or misaligned (PSF_E_SHAPE); per MLP NULL / 2-byte
+ *   alignment; per step NULL, 16-byte alignment, out == V0 or out == the step's input (PSF_E_ALIAS). B == 0 then returns 0.
+ *   No allocation, no synchronisation; capturable in a HIP graph. Added without a version change (additive).
+ */
+int32_t psf_mixer_fwd_bf16_plan(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L);
+int64_t psf_mixer_fwd_bf16_workspace(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L);
+int psf_mixer_fwd_bf16(const uint16_t* X, int64_t B, int64_t N, int32_t E, int32_t M, const uint16_t* const* A,
+                       const uint16_t* const* a, const uint16_t* const* Bw, const uint16_t* const* b, const int32_t* h, int64_t C,
+                       int32_t L, int32_t use_residual, uint16_t* V0, uint16_t* const* out_steps, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
+/*
  * The same with `data` itself never in memory: X is replaced by the recipe PSFNet.forward computes it by, and every kernel
  * of the mixer evaluates the rows it needs from that recipe (a step then reads 8 bytes per position instead of 4 E).
  *   PSF_MIXER_IN_DATA    src = float X [B,N,E]                                        (psf_mixer_fwd_f32)
@@ -527,7 +559,8 @@ int psf_stream_mix_bwd_f32(const float* w, const float* v, const float* z, float
  *                      (psf_chord_chain_fwd_f32 above); 0 keeps the per-step launches, which write every step.
  *   "chain_bwd_fused": 0 makes psf_chord_chain_bwd_f32 / _bf16 return PSF_E_UNSUPPORTED and
  *                      psf_chord_chain_bwd_supported return 0: the caller runs the steps itself.
- *   "mixer_lds"      : 0 takes the single-launch mixer away: psf_mixer_fwd_plan answers 1 (or 0) instead of 2, an input
+ *   "mixer_lds"      : 0 takes the single-launch mixer away: psf_mixer_fwd_bf16_plan answers 0 and psf_mixer_fwd_bf16 returns
+ *                      PSF_E_UNSUPPORTED; psf_mixer_fwd_plan answers 1 (or 0) instead of 2, an input
  *                      recipe (psf_mixer_fwd_in_f32 with another kind than PSF_MIXER_IN_DATA) returns PSF_E_SHAPE, and a
  *                      shape that only the single launch covers returns PSF_E_TUNING.
  * Every other key ("wide_fuse" among them: same arithmetic in the same order) changes time only.

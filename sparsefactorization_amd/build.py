@@ -26,10 +26,10 @@ ARCH = "gfx950"
 WIN_TGS = list(range(7))
 
 HEADERS = ["psf_common.h", "fwd_kernels.h", "fwd_window.h", "fwd_window_launch.h", "bwd_kernels.h",
-           "bwd_window.h", "bwd_dw_chunk.h", "bwd_window_launch.h", "bwd_fused.h", "bwd_fused_bf16.h", "fwd_chain_lds.h", "fwd_chain_lds_bf16.h", "fwd_chain_lds_launch.h", "bwd_chain_lds.h", "fwd_mlp_step.h", "fwd_mlp_step_launch.h", "mixer_lds.h", "mixer_lds_launch.h", "mlp_x3_image.h", "mlp_bf16_image.h", "mlp_fwd_x3.h", "mlp_x3_common.h", "mlp_planes.h", "x3_gemm.h",
+           "bwd_window.h", "bwd_dw_chunk.h", "bwd_window_launch.h", "bwd_fused.h", "bwd_fused_bf16.h", "fwd_chain_lds.h", "fwd_chain_lds_bf16.h", "fwd_chain_lds_launch.h", "bwd_chain_lds.h", "fwd_mlp_step.h", "fwd_mlp_step_launch.h", "mixer_lds.h", "mixer_lds_launch.h", "mixer_lds_bf16.h", "mixer_lds_bf16_launch.h", "mlp_x3_image.h", "mlp_bf16_image.h", "mlp_bf16_tile.h", "mlp_fwd_x3.h", "mlp_x3_common.h", "mlp_planes.h", "x3_gemm.h",
            os.path.join("..", "..", "include", "psf_chord.h"), os.path.join("..", "..", "include", "psf_chord_tuning.h")]
 SOURCES = ["psf_chord.hip", "fwd_window_inst.hip", "bwd_window_inst.hip", "bwd_fused_bf16_inst.hip", "linear_wgrad.hip",
-           "fwd_chain_lds_inst.hip", "fwd_chain_lds_bf16_inst.hip", "bwd_chain_lds_inst.hip", "fwd_mlp_step_inst.hip", "mixer_lds_inst.hip", "embed.hip", "flat_head.hip", "sum_tensors.hip", "adam.hip", "mlp_fwd.hip", "mlp_fwd_x3.hip", "mlp_fwd_bf16.hip", "mlp_bwd.hip", "mlp_wide.hip", "stream_mix.hip"]
+           "fwd_chain_lds_inst.hip", "fwd_chain_lds_bf16_inst.hip", "bwd_chain_lds_inst.hip", "fwd_mlp_step_inst.hip", "mixer_lds_inst.hip", "mixer_lds_bf16_inst.hip", "embed.hip", "flat_head.hip", "sum_tensors.hip", "adam.hip", "mlp_fwd.hip", "mlp_fwd_x3.hip", "mlp_fwd_bf16.hip", "mlp_bwd.hip", "mlp_wide.hip", "stream_mix.hip"]
 
 # -ffp-contract=off: products and sums stay separate roundings (bitwise parity with the CPU oracle).
 HIPCC_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
@@ -89,6 +89,8 @@ def _unit_table():
              (os.path.join(OBJ_DIR, "adam.o"), os.path.join(CSRC, "adam.hip"), []),
              (os.path.join(OBJ_DIR, "stream_mix.o"), os.path.join(CSRC, "stream_mix.hip"), []),
              (os.path.join(OBJ_DIR, "mixer_lds.o"), os.path.join(CSRC, "mixer_lds_inst.hip"), []),
+             # the bf16 single-launch mixer: a unit of its own (the name keeps it under R3_STRICT_UNITS' "mixer_lds")
+             (os.path.join(OBJ_DIR, "mixer_lds_bf16.o"), os.path.join(CSRC, "mixer_lds_bf16_inst.hip"), []),
              (os.path.join(OBJ_DIR, "mlp_fwd.o"), os.path.join(CSRC, "mlp_fwd.hip"), []),
              (os.path.join(OBJ_DIR, "mlp_fwd_x3.o"), os.path.join(CSRC, "mlp_fwd_x3.hip"), []),
              # the bf16 producer forward: a unit of its own, so the f32 producer units' ISA is what it was

@@ -20,15 +20,14 @@
 #include <stdint.h>
 
 #include "../../include/psf_chord.h"
-#include "mlp_bf16_image.h"
-#include "mlp_x3_common.h"
-#include "mlp_x3_image.h"  // gelu2
+#include "mlp_bf16_tile.h"
 
 extern "C" int psf_internal_fail(int code, const char* message);
 
 namespace {
 
 namespace mb = psf_mlp_bf16;  // (qualified: mlp_x3_image.h has constants of the same names in this unnamed namespace)
+using mb::bf16_rne_bits;
 using psf_x3::bf16x8;
 using psf_x3::cd_row;
 using psf_x3::f32x16;
@@ -58,22 +57,6 @@ __global__ void __launch_bounds__(256) mlp_bf16_pack_k(const mb::Args a) {
     const int rho = (i & 3) + 16 * s + 8 * (i >> 2) + 4 * hf;
     img16[mb::kOffB / 2 + q] = (o < d.O && ht + rho < d.h) ? d.B[o * d.h + ht + rho] : (uint16_t)0;
   }
-}
-
-// f32 -> bf16, round to nearest even, a NaN stays a NaN (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ uint16_t bf16_rne_bits(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
-
-// registers 8 s .. 8 s + 7 of GEMM1's accumulator -> the B fragment of GEMM2's k-step s: round, widen, GELU, round
-__device__ __forceinline__ bf16x8 gelu_frag(const f32x16& acc1, int s) {
-  bf16x8 f;
-#pragma unroll
-  for (int i = 0; i < 8; i += 2) {
-    const float z0 = (float)(__bf16)acc1[8 * s + i], z1 = (float)(__bf16)acc1[8 * s + i + 1];
-    const f32x2 y = gelu2(f32x2{z0, z1});
-    f[i] = (__bf16)y.x;
-    f[i + 1] = (__bf16)y.y;
-  }
-  return f;
 }
 
 // The LDS-DMA of an image is counted by vmcnt and by nothing else: hipcc puts no vmcnt wait in front of a workgroup barrier
@@ -123,27 +106,9 @@ __global__ void __launch_bounds__(256, 4) mlp_fwd_bf16_k(const mb::Args a) {
       __syncthreads();  // image u has landed in every wave's view; unit u-1 is finished
       if (u + 1 < U) stage(u + 1);
       const unsigned char* img = lds_raw + (u & 1) * mb::kImgBytes;
-      const float* sa = reinterpret_cast<const float*>(img + mb::kOffSa);
-      const float* sb = reinterpret_cast<const float*>(img + mb::kOffSb);
       const uint32_t ut = a.unit[u];
       const bool first = ((ut >> 8) & 0xff) == 0, last = (ut >> 16) != 0;
-
-      bf16x8 wa[KS], wb[2];
-#pragma unroll
-      for (int s = 0; s < KS; ++s) wa[s] = *reinterpret_cast<const bf16x8*>(img + c * mb::kARow + 32 * s + 16 * half);
-#pragma unroll
-      for (int s = 0; s < 2; ++s) wb[s] = *reinterpret_cast<const bf16x8*>(img + mb::kOffB + ((s * 2 + half) * 32 + c) * 16);
-      f32x16 acc1;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc1[r] = sa[cd_row(r, half)];
-      if (first) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc2[r] = sb[cd_row(r, half)];
-      }
-#pragma unroll
-      for (int s = 0; s < KS; ++s) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[s], xf[s], acc1, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[0], gelu_frag(acc1, 0), acc2, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[1], gelu_frag(acc1, 1), acc2, 0, 0, 0);
+      mb::mlp_unit<KS, false>(img, xf, first, acc2, c, half);
 
       if (last && rows > 0) {
         const mb::Mlp& dp = a.m[ut & 0xff];
@@ -185,6 +150,12 @@ void fill_args(const uint32_t* unit, int32_t U, const uint16_t* X, int64_t T, in
 }
 
 }  // namespace
+
+// the pack kernel for the other unit that evaluates these images (mixer_lds_bf16_inst.hip): Y of args.m[] is not read
+hipError_t psf_mlp_bf16::pack_launch(const psf_mlp_bf16::Args& args, hipStream_t s) {
+  hipLaunchKernelGGL(mlp_bf16_pack_k, dim3(args.U), dim3(256), 0, s, args);
+  return hipGetLastError();
+}
 
 extern "C" {
 

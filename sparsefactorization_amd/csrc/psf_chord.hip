@@ -23,6 +23,7 @@
 #include "fwd_kernels.h"
 #include "fwd_mlp_step_launch.h"
 #include "fwd_window_launch.h"
+#include "mixer_lds_bf16_launch.h"
 #include "mixer_lds_launch.h"
 #include "mlp_fwd_x3.h"
 
@@ -972,6 +973,7 @@ const char* psf_build_info(void) {
          " | bf16 chord path: f32 accumulation, one rounding per element; fwd: generic + LDS-window<bf16, TG<=16, NT=256, R=2>; bwd: fused dV+dW step<bf16, TG<=16, NT=256> (aligned full tiles), LDS-window dV<R=2> / dW<R=1><bf16, TG<=16> + generic;"
          " backward chain issued by the library (per-step launches)"
          " | bf16 producers: fused MLP fwd<bf16> (one MFMA term, hidden layer in registers, E <= 64, inference)"
+         " | bf16 mixer: one LDS-resident launch for short sequences (N <= 512, C = 8 or 16), the bits of the two-call route"
          " | arithmetic of the chord path: uncontracted mul+add (bf16: exact products fused), links ascending"
 #ifdef PSF_CSRC_HASH
          " | csrc=" PSF_CSRC_HASH  // build.csrc_hash() of the sources this library was built from (_lib.load compares)
@@ -1235,6 +1237,71 @@ int psf_mixer_fwd_f32(const float* X, int64_t B, int64_t N, int32_t E, int32_t M
   psf_mixer_input in;
   in.kind = PSF_MIXER_IN_DATA, in.K = 0, in.src = X, in.weight = in.bias = in.pos = nullptr;
   return psf_mixer_fwd_in_f32(&in, B, N, E, M, A, a, Bw, b, h, C, L, use_residual, V0, out_steps, workspace, workspace_bytes, stream);
+}
+
+int32_t psf_mixer_fwd_bf16_plan(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
+  MixerLdsBf16Plan p;
+  return (g_mixer_lds.load() && plan_mixer_lds_bf16(N, E, M, h, C, L, &p)) ? 2 : 0;
+}
+
+int64_t psf_mixer_fwd_bf16_workspace(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
+  MixerLdsBf16Plan p;
+  if (!plan_mixer_lds_bf16(N, E, M, h, C, L, &p)) return -1;
+  return (int64_t)p.units * psf_mlp_bf16::kImgBytes;
+}
+
+int psf_mixer_fwd_bf16(const uint16_t* X, int64_t B, int64_t N, int32_t E, int32_t M, const uint16_t* const* A,
+                       const uint16_t* const* a, const uint16_t* const* Bw, const uint16_t* const* b, const int32_t* h, int64_t C,
+                       int32_t L, int32_t use_residual, uint16_t* V0, uint16_t* const* out_steps, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  if (!X || !A || !a || !Bw || !b || !h || !out_steps || !workspace) return fail(PSF_E_NULL, "psf_mixer_fwd_bf16: NULL argument");
+  if (B < 0 || B > 0x7fffffff) return fail(PSF_E_SHAPE, "psf_mixer_fwd_bf16: need 0 <= B < 2^31 (got B=%lld)", (long long)B);
+  MixerLdsBf16Plan mp;
+  if (!plan_mixer_lds_bf16(N, E, M, h, C, L, &mp))
+    return fail(PSF_E_UNSUPPORTED, "psf_mixer_fwd_bf16: no kernel for N=%lld E=%d M=%d C=%lld L=%d (psf_mixer_fwd_bf16_plan): run "
+                "psf_mlp_fwd_bf16 and psf_chord_chain_fwd_bf16", (long long)N, (int)E, (int)M, (long long)C, (int)L);
+  if (!g_mixer_lds.load()) return fail(PSF_E_UNSUPPORTED, "psf_mixer_fwd_bf16: mixer_lds=0 takes the single-launch mixer away");
+  if (!aligned_to(X, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: X must be 16-byte aligned");
+  if (V0 && !aligned_to(V0, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: V0 must be 16-byte aligned");
+  if (workspace_bytes < (int64_t)mp.units * psf_mlp_bf16::kImgBytes || !aligned_to(workspace, 16))
+    return fail(PSF_E_SHAPE, "psf_mixer_fwd_bf16: workspace too small (psf_mixer_fwd_bf16_workspace) or not 16-byte aligned");
+  for (int k = 0; k <= M; ++k) {
+    if (!A[k] || !a[k] || !Bw[k] || !b[k]) return fail(PSF_E_NULL, "psf_mixer_fwd_bf16: NULL layer pointer (MLP %d)", k);
+    if (!aligned_to(A[k], 2) || !aligned_to(a[k], 2) || !aligned_to(Bw[k], 2) || !aligned_to(b[k], 2))
+      return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: weights and biases must be 2-byte aligned (MLP %d)", k);
+  }
+  for (int m = 0; m < M; ++m) {
+    if (!out_steps[m]) return fail(PSF_E_NULL, "psf_mixer_fwd_bf16: step %d: NULL output", m);
+    if (!aligned_to(out_steps[m], 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: step %d: output not 16-byte aligned", m);
+    if (out_steps[m] == V0) return fail(PSF_E_ALIAS, "psf_mixer_fwd_bf16: step %d: out aliases V0", m);
+    if (m > 0 && out_steps[m] == out_steps[m - 1]) return fail(PSF_E_ALIAS, "psf_mixer_fwd_bf16: step %d: out aliases the step's input", m);
+  }
+  if (B == 0) return PSF_OK;
+
+  int32_t O[32];
+  O[0] = (int32_t)C;
+  for (int k = 1; k <= M; ++k) O[k] = L;
+  psf_mlp_bf16::Args pack;
+  if (!psf_mlp_bf16::make_plan(E, M + 1, h, O, pack.unit, &pack.U)) return fail(PSF_E_SHAPE, "psf_mixer_fwd_bf16: unit plan");
+  for (int k = 0; k < psf_mlp_bf16::kMaxK; ++k)
+    pack.m[k] = k <= M ? psf_mlp_bf16::Mlp{A[k], a[k], Bw[k], b[k], nullptr, h[k], O[k]} : psf_mlp_bf16::Mlp{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+  pack.X = X;
+  pack.images = reinterpret_cast<unsigned char*>(workspace);
+  pack.T = B * N;
+  pack.E = E;
+  MixerLdsBf16Args la;
+  la.X = X;
+  la.images = pack.images;
+  la.first_unit[0] = 0;
+  for (int k = 0; k <= M; ++k) la.first_unit[k + 1] = la.first_unit[k] + (h[k] + 31) / 32;
+  la.V0 = V0;
+  for (int m = 0; m < kMixerLdsBf16MaxSteps; ++m) la.out[m] = m < M ? out_steps[m] : nullptr;
+  la.store_mask = (uint32_t)chain_store_mask(out_steps, M);  // a buffer that a later step overwrites is not stored at all
+  la.M = M, la.N = (int32_t)N, la.C = (int32_t)C, la.E = E, la.L = L, la.CG = (int32_t)(C / 8), la.WS = mp.WS, la.TT = (int32_t)(N / 32);
+  Offsets offs;
+  make_offsets(N, L, nullptr, &offs);
+  const hipError_t e = launch_mixer_lds_bf16(mp, use_residual != 0, pack, la, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
+  return e == hipSuccess ? PSF_OK : fail_hip(e, "chord_mixer_lds<bf16> launch");
 }
 
 int psf_set_tuning(const char* key, int32_t value) {

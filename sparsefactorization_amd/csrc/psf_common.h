@@ -182,6 +182,10 @@ __device__ __forceinline__ uint32_t lane_off(uint32_t v) {
 // clobber does not do that: hipcc is free to linearise register-only arithmetic in front of it, and did (the first
 // "fixed" build had its wait behind most of the row's multiplies — r04b, "What the ISA says").
 __device__ __forceinline__ void lds_wait_all() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// The LDS-DMA (global_load_lds) of a weight image is counted by vmcnt and by nothing else, and hipcc puts no vmcnt wait in
+// front of a workgroup barrier for it (mlp_fwd_bf16.hip: dma_wait): every wave drains its own pieces before the barrier that
+// publishes the image; behind the barrier all pieces have landed.
+__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void behind_wait(float& r) { asm volatile("" : "+v"(r)); }
 __device__ __forceinline__ void behind_wait(float __attribute__((ext_vector_type(4))) & r) { asm volatile("" : "+v"(r)); }
 template <int VEC>

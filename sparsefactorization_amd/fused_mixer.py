@@ -29,6 +29,11 @@ route = "auto"
 #: 0.97 against 0.82 ms per Adding forward; profiles/r04h_mixer_bench.log, r04w_bench_stdout.log) and round 5 removed those
 #: instances (two thirds of that translation unit).
 recipe_in_kernel = False
+#: A bf16 model's short sequences: the whole mixer in ONE launch (psf_mixer_fwd_bf16, csrc/mixer_lds_bf16.h) instead of
+#: psf_mlp_fwd_bf16 + psf_chord_chain_fwd_bf16 — the same bits. "never": the two calls, as before; "always": wherever
+#: ``covered_bf16`` holds and nothing needs a gradient. The default stays "never" until the numbers of
+#: profiles/bf16_mixer_ab.md are acted on.
+bf16_route = "never"
 
 
 class Recipe:
@@ -90,15 +95,17 @@ class Recipe:
         return s.dim() == 2 and s.dtype == torch.int64 and self.weight.dtype == torch.float32 and self.weight.dim() == 2
 
 
-def _block_pairs(E: int, g: nn.Module, fs: Sequence[nn.Module]):
-    """((M, h table, C, L), [(lin1, lin2), ...]) when every block is Linear, GELU(erf), Linear of input width E and the link
-    MLPs agree on L; None otherwise."""
+def _block_pairs(E: int, g: nn.Module, fs: Sequence[nn.Module], dtype: torch.dtype = torch.float32):
+    """((M, h table, C, L), [(lin1, lin2), ...]) when every block is Linear, GELU(erf), Linear of input width E in ``dtype`` and
+    the link MLPs agree on L; None otherwise. (f32: the first layer's weight decides, as ever; bf16: all four parameters.)"""
     if not len(fs):
         return None
     pairs = [_two_layer(b) for b in [g, *fs]]
     if any(p is None for p in pairs):
         return None
-    if any(l1.in_features != E or l1.weight.dtype != torch.float32 for l1, _ in pairs):
+    if any(l1.in_features != E or l1.weight.dtype != dtype for l1, _ in pairs):
+        return None
+    if dtype != torch.float32 and any(p.dtype != dtype for l1, l2 in pairs for p in (l1.bias, l2.weight, l2.bias)):
         return None
     L = pairs[1][1].out_features
     if any(l2.out_features != L for _, l2 in pairs[1:]):
@@ -215,3 +222,59 @@ def covered(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
 def mixer_forward(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module], use_residual: bool) -> torch.Tensor:
     """V_M [B, N, C] from ``data`` [B, N, E]. Caller checks ``eligible`` (or ``covered``) first."""
     return mixer_forward_in(Recipe.data(x), g, fs, use_residual)
+
+
+# ---------------------------------------------------------------------------------------------------
+# bf16: the single-launch mixer of short sequences (psf_mixer_fwd_bf16)
+# ---------------------------------------------------------------------------------------------------
+def _found_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]):
+    """What ``_block_pairs`` finds for bf16 ``data`` [B, N, E] on the GPU that psf_mixer_fwd_bf16 covers, or None."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or not x.is_cuda or x.dtype != torch.bfloat16:
+        return None
+    found = _block_pairs(x.shape[-1], g, fs, torch.bfloat16)
+    if found is None:
+        return None
+    M, h, C, L = found[0]
+    return found if _lib.load().psf_mixer_fwd_bf16_plan(x.shape[1], x.shape[-1], M, h, C, L) == 2 else None
+
+
+def covered_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
+    """bf16 ``data`` [B, N, E] on the GPU, every block Linear -> GELU(erf) -> Linear in bf16, the link MLPs agreeing on L, and a
+    shape the single launch takes (psf_mixer_fwd_bf16_plan == 2) — whatever ``bf16_route`` says about using it."""
+    return _found_bf16(x, g, fs) is not None
+
+
+def find_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]):
+    """``found`` for ``mixer_forward_bf16`` when ``bf16_route`` wants the single launch, it covers the call and nothing needs a
+    gradient; None otherwise."""
+    if not enabled or bf16_route != "always" or _needs_grad(x, [g, *fs]):
+        return None
+    return _found_bf16(x, g, fs)
+
+
+def mixer_forward_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module], use_residual: bool, found=None) -> torch.Tensor:
+    """V_M [B, N, C] in bf16 from bf16 ``data`` [B, N, E]: the bits of ``fused_mlp_forward_bf16`` + ``chord_chain``. Two ping-pong
+    step buffers, as ``mixer_forward_in``. Caller checks ``covered_bf16`` (or passes what ``find_bf16`` returned)."""
+    if found is None:
+        found = _found_bf16(x, g, fs)
+        if found is None:
+            raise ValueError("psf_mixer_fwd_bf16 does not cover this call: bf16 data [B, N, E] on the GPU, every block "
+                             "Linear(E, h) -> GELU(erf) -> Linear(h, out) in bf16, the link MLPs agreeing on L (check covered_bf16())")
+    (M, h, C, L), pairs = found
+    B, N, E = x.shape
+    dev = x.device
+    lib = _lib.load()
+    x = x.detach().contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    params = [p.detach().contiguous() for l1, l2 in pairs for p in (l1.weight, l1.bias, l2.weight, l2.bias)]
+    ws_bytes = lib.psf_mixer_fwd_bf16_workspace(N, E, M, h, C, L)
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    bufs = [torch.empty((B, N, C), dtype=torch.bfloat16, device=dev) for _ in range(min(M, 2))]
+    o_tab = (ctypes.c_void_p * M)(*[bufs[m % len(bufs)].data_ptr() for m in range(M)])
+    with torch.cuda.device(dev):
+        rc = lib.psf_mixer_fwd_bf16(x.data_ptr(), B, N, E, M, _ptrs(params[0::4]), _ptrs(params[1::4]), _ptrs(params[2::4]),
+                                    _ptrs(params[3::4]), h, C, L, 1 if use_residual else 0, None, o_tab, ws.data_ptr(), ws.numel(),
+                                    _lib.stream_ptr(dev))
+    _lib.check(rc, "psf_mixer_fwd_bf16")
+    return bufs[(M - 1) % len(bufs)]
