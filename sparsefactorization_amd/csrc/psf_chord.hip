@@ -4,9 +4,10 @@
 // (and its copies) and spmul_cuda.{forward_host,backward_host} (spmul/spmul_cuda.cu:31-59,114-159).
 // Stateless apart from a thread-local error string and a few process-wide tuning integers.
 //
-// Every step is planned once (plan_fwd / plan_bwd / plan_chain fill a plain struct) and the plan is either executed
-// (fwd_impl / bwd_impl / chain_impl, from the caller's pointers) or printed (psf_describe_*, operands taken as aligned:
-// nullptr, which aligned_to accepts). The order of the picks, the gates and the thresholds exist in the planners only.
+// Every step is planned once (plan_fwd / plan_bwd / plan_chain, and plan_mixer / plan_mixer_bf16 for the mixers, fill a plain
+// struct) and the plan is either executed (fwd_impl / bwd_impl / chain_impl / mixer_impl / mixer_bf16_impl, from the caller's
+// pointers), printed (psf_describe_*, operands taken as aligned: nullptr, which aligned_to accepts) or reported
+// (psf_mixer_fwd*_plan / *_workspace). The order of the picks, the gates and the thresholds exist in the planners only.
 
 #include <atomic>
 #include <cstdarg>
@@ -899,40 +900,211 @@ int chain_bwd_impl(const K* dOut, const K* const* W_steps, const K* V0, const K*
 // ------------------------------------------------------------------------------------------------------
 // the mixer with W computed inside the step (fwd_mlp_step.h)
 // ------------------------------------------------------------------------------------------------------
+enum class MixerRoute { kNone, kLds, kSteps };  // kNone: only the LDS-resident kernel covers the shape and this snapshot keeps it away
 struct MixerPlan {
-  bool step_ok;            // the per-step kernels (fwd_mlp_step.h) cover the shape
-  bool lds_ok;             // the single-launch LDS-resident kernel (mixer_lds.h) covers it
-  int tgs, TR, KN, units;  // units = packed images over all M + 1 MLPs
+  bool covered;      // one of the two kernel families covers the shape (psf_mixer_fwd_workspace() >= 0)
+  int units;         // packed images over all M + 1 MLPs
+  int64_t ws_bytes;  // ... in bytes; -1 when not covered
+  MixerRoute route;  // kLds: the single-launch LDS-resident kernel (mixer_lds.h, `lds`); kSteps: the per-step kernels (fwd_mlp_step.h)
   MixerLdsPlan lds;
+  WinPick pk;        // kSteps: the tiles of every launch, pk.all_edge for the M steps
+  bool g_all_edge;   // ... and for the g launch
 };
 
-// Whether the fused paths cover the shape; fills *mp. Mirrors the limits stated in include/psf_chord.h.
-bool plan_mixer(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L, MixerPlan* mp) {
+// The mixer of one shape under one snapshot. Mirrors the limits stated in include/psf_chord.h. B enters the route (the LDS
+// kernel's grid) and the tile decision only: the queries, which have no B, plan with B = 1.
+MixerPlan plan_mixer(const Tuning& tn, int64_t B, int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
+  MixerPlan p{};
+  p.ws_bytes = -1;
   if (!h || M < 1 || M > 31 || E < 4 || E > 32 || (E & 3) || C < 4 || C > 32 || (C & 3) || L < kMlpStepLmin || L > kMlpStepLmax ||
       N < 1 || N > (int64_t)1 << 30)
-    return false;
+    return p;
   int units = 0, nu_max = 0;
   for (int k = 0; k <= M; ++k) {
-    if (h[k] < 1 || h[k] > 128) return false;
+    if (h[k] < 1 || h[k] > 128) return p;
     const int nu = (h[k] + 31) / 32;
-    units += nu;
-    nu_max = nu > nu_max ? nu : nu_max;
+    units += nu, nu_max = nu > nu_max ? nu : nu_max;
   }
-  if (units > 128) return false;
-  mp->units = units;
-  mp->lds_ok = plan_mixer_lds(N, C, L, M, nu_max, &mp->lds);
-  mp->step_ok = false;
-  const int tgs = ceil_log2(C / 4);
-  if (tgs <= kMlpStepTgsMax) {
-    const int TR = mlp_step_tile_rows(tgs);
-    if (N >= 2 * (int64_t)TR) {  // the window may wrap at most once
-      Offsets offs;
-      make_offsets(N, L, nullptr, &offs);
-      const int KN = near_links(TR, L, offs);
-      if (KN) mp->step_ok = true, mp->tgs = tgs, mp->TR = TR, mp->KN = KN;
-    }
+  if (units > 128) return p;
+  const bool lds_ok = plan_mixer_lds(N, C, L, M, nu_max, &p.lds);
+  const int tgs = ceil_log2(C / 4), TR = tgs <= kMlpStepTgsMax ? mlp_step_tile_rows(tgs) : 0;
+  Offsets offs;
+  make_offsets(N, L, nullptr, &offs);
+  const int KN = TR && N >= 2 * (int64_t)TR ? near_links(TR, L, offs) : 0;  // (the window may wrap at most once) 0: no per-step kernel
+  if (!lds_ok && !KN) return p;
+  p.covered = true, p.units = units, p.ws_bytes = (int64_t)units * kX3ImageBytes;
+  p.route = lds_ok && tn.mixer_lds && B <= 0x7fffffff ? MixerRoute::kLds : KN ? MixerRoute::kSteps : MixerRoute::kNone;
+  if (p.route != MixerRoute::kSteps) return p;
+  // the tile geometry of every per-step launch
+  set_pick(&p.pk, tgs, mlp_step_rows(tgs), 256, TR, KN, N);
+  const int TG = 1 << tgs;
+  // The step kernel's full-tile instance takes every row block as TR-aligned (scalar block addresses, fwd_mlp_step.h): N and
+  // every far offset multiples of TR, rows of exactly 4 TG channels, a batch element under 2^31 bytes; anything else runs the
+  // predicated instance on every tile. (ragged_in_one_launch's E: this step moves the data row, not the W row.)
+  bool blocks_aligned = (N % TR) == 0 && C == 4 * (int64_t)TG && N * C * 4 < ((int64_t)1 << 31) && N * (int64_t)E * 4 < ((int64_t)1 << 31);
+  for (int k = KN; k < L; ++k) blocks_aligned = blocks_aligned && (offs.v[k] % TR) == 0;
+  // (the entry plans before it has looked at B: one that it then turns away, B < 0 or B * N > 2^40, stays out of the product)
+  const int64_t Bt = B < 0 || B > ((int64_t)1 << 40) / N ? 0 : B;
+  p.pk.all_edge = !blocks_aligned || !tn.fwd_split || ragged_in_one_launch(tn, p.pk.ragged, Bt, N, E, C);
+  p.g_all_edge = p.pk.ragged && p.pk.all_edge;  // the g kernel needs its predicate only for rows >= N
+  return p;
+}
+
+// The bf16 mixer has the single launch only (mixer_lds_bf16.h): its limits (plan_mixer_lds_bf16) and the knob.
+struct MixerBf16Plan {
+  bool covered, run;  // inside the limits; ... and mixer_lds lets it run
+  int64_t ws_bytes;   // -1 when not covered
+  MixerLdsBf16Plan lds;
+};
+
+MixerBf16Plan plan_mixer_bf16(const Tuning& tn, int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
+  MixerBf16Plan p{};
+  p.covered = plan_mixer_lds_bf16(N, E, M, h, C, L, &p.lds);
+  p.run = p.covered && tn.mixer_lds;
+  p.ws_bytes = p.covered ? (int64_t)p.lds.units * psf_mlp_bf16::kImgBytes : -1;
+  return p;
+}
+
+// The four layer tables of mixer entry `who`: every MLP's pointers non-NULL and aligned to `align` bytes (1: not looked at).
+template <typename T>
+int check_layer_tables(const char* who, const T* const* A, const T* const* a, const T* const* Bw, const T* const* b, int32_t M, size_t align) {
+  for (int k = 0; k <= M; ++k) {
+    if (!A[k] || !a[k] || !Bw[k] || !b[k]) return fail(PSF_E_NULL, "%s: NULL layer pointer (MLP %d)", who, k);
+    if (!aligned_to(A[k], align) || !aligned_to(a[k], align) || !aligned_to(Bw[k], align) || !aligned_to(b[k], align))
+      return fail(PSF_E_ALIGN, "%s: weights and biases must be %d-byte aligned (MLP %d)", who, (int)align, k);
   }
-  return mp->step_ok || mp->lds_ok;
+  return PSF_OK;
+}
+
+// ... and its step outputs: non-NULL, 16-byte aligned, none of them V0 or its own step's input.
+template <typename T>
+int check_out_steps(const char* who, T* const* out_steps, const T* V0, int32_t M) {
+  for (int m = 0; m < M; ++m) {
+    if (!out_steps[m]) return fail(PSF_E_NULL, "%s: step %d: NULL output", who, m);
+    if (!aligned_to(out_steps[m], 16)) return fail(PSF_E_ALIGN, "%s: step %d: output not 16-byte aligned", who, m);
+    if (out_steps[m] == V0) return fail(PSF_E_ALIAS, "%s: step %d: out aliases V0", who, m);
+    if (m > 0 && out_steps[m] == out_steps[m - 1]) return fail(PSF_E_ALIAS, "%s: step %d: out aliases the step's input", who, m);
+  }
+  return PSF_OK;
+}
+
+int mixer_impl(Tuning tn, const psf_mixer_input* in, int64_t B, int64_t N, int32_t E, int32_t M, const float* const* A,
+               const float* const* a, const float* const* Bw, const float* const* b, const int32_t* h, int64_t C, int32_t L,
+               int32_t use_residual, float* V0, float* const* out_steps, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!in || !in->src || !A || !a || !Bw || !b || !h || !V0 || !out_steps || !workspace)
+    return fail(PSF_E_NULL, "psf_mixer_fwd: NULL argument");
+  MixerIn mi;
+  mi.src = in->src, mi.weight = in->weight, mi.bias = in->bias, mi.pos = in->pos, mi.kind = in->kind, mi.K = in->K;
+  if (in->kind == PSF_MIXER_IN_DATA) {
+    mi.weight = mi.bias = mi.pos = nullptr, mi.K = 0;
+    if (!aligned_to(in->src, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd: X must be 16-byte aligned");
+  } else if (in->kind == PSF_MIXER_IN_AFFINE) {
+    if (in->K < 1 || in->K > 3) return fail(PSF_E_SHAPE, "psf_mixer_fwd: the affine input takes 1..3 values per position (K=%d)", (int)in->K);
+    if (!in->weight) return fail(PSF_E_NULL, "psf_mixer_fwd: affine input without a weight");
+    if (!aligned_to(in->src, 4) || !aligned_to(in->weight, 4) || (in->bias && !aligned_to(in->bias, 4)))
+      return fail(PSF_E_ALIGN, "psf_mixer_fwd: affine input pointers must be 4-byte aligned");
+  } else if (in->kind == PSF_MIXER_IN_TOKENS) {
+    if (in->K < 1) return fail(PSF_E_SHAPE, "psf_mixer_fwd: empty vocabulary");
+    if (!in->weight) return fail(PSF_E_NULL, "psf_mixer_fwd: token input without a table");
+    if (!aligned_to(in->src, 8) || !aligned_to(in->weight, 16))
+      return fail(PSF_E_ALIGN, "psf_mixer_fwd: tokens must be 8-byte, the table 16-byte aligned");
+    mi.bias = nullptr;
+  } else {
+    return fail(PSF_E_SHAPE, "psf_mixer_fwd: unknown input kind %d", (int)in->kind);
+  }
+  if (mi.pos && !aligned_to(mi.pos, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd: pos must be 16-byte aligned");
+  const MixerPlan mp = plan_mixer(tn, B, N, E, M, h, C, L);
+  if (!mp.covered)
+    return fail(PSF_E_SHAPE, "psf_mixer_fwd: shape outside the fused path (N=%lld E=%d M=%d C=%lld L=%d; see psf_mixer_fwd_workspace)",
+                (long long)N, (int)E, (int)M, (long long)C, (int)L);
+  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
+  if (in->kind != PSF_MIXER_IN_DATA && mp.route != MixerRoute::kLds)  // (before anything is launched)
+    return fail(PSF_E_SHAPE, "psf_mixer_fwd: an input recipe (kind %d) is evaluated by the single-launch kernel only (short sequences, "
+                "psf_mixer_fwd_plan() == 2); for N=%lld write the rows with psf_affine_rows_f32 / psf_embed_tokens_f32 and pass them",
+                (int)in->kind, (long long)N);
+  if (B == 0) return PSF_OK;
+  if (workspace_bytes < mp.ws_bytes || !aligned_to(workspace, 16))
+    return fail(PSF_E_SHAPE, "psf_mixer_fwd: workspace too small (psf_mixer_fwd_workspace) or not 16-byte aligned");
+  if (!aligned_to(V0, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd: V0 must be 16-byte aligned");
+  if (B * N > (int64_t)1 << 40) return fail(PSF_E_SHAPE, "psf_mixer_fwd: B*N too large");
+  if (int rc = check_layer_tables("psf_mixer_fwd", A, a, Bw, b, M, 1)) return rc;
+  if (int rc = check_out_steps<float>("psf_mixer_fwd", out_steps, V0, M)) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // (1) all M + 1 weight sets -> unit images (one launch)
+  int32_t O[32], first_unit[33];
+  for (int k = 0; k <= M; ++k) O[k] = k ? L : (int32_t)C;
+  hipError_t e = psf_x3_pack_launch(E, M + 1, A, a, Bw, b, h, O, workspace, first_unit, s);
+  if (e != hipSuccess) return fail_hip(e, "psf_mixer_fwd: pack");
+  Offsets offs;
+  make_offsets(N, L, nullptr, &offs);
+  if (mp.route == MixerRoute::kLds) {  // short sequences: the whole mixer in ONE launch, V resident in LDS
+    MixerLdsArgs la;
+    la.in = mi, la.images = reinterpret_cast<const unsigned char*>(workspace), la.V0 = V0;
+    for (int k = 0; k <= M + 1; ++k) la.first_unit[k] = first_unit[k];
+    for (int m = 0; m < kMixerLdsMaxSteps; ++m) la.out[m] = m < M ? out_steps[m] : nullptr;
+    la.store_mask = (uint32_t)chain_store_mask(out_steps, M);  // a buffer that a later step overwrites (two-buffer inference) is not stored at all
+    la.M = M, la.N = (int32_t)N, la.C = (int32_t)C, la.E = E, la.L = L, la.CG = (int32_t)(C / 4), la.WS = mp.lds.WS;
+    la.TT = (int32_t)(N / 32), la.nu_max = mp.lds.nu_max;
+    e = launch_mixer_lds(mp.lds, use_residual != 0, la, offs, (int)B, s);
+    return e == hipSuccess ? PSF_OK : fail_hip(e, "chord_mixer_lds launch");
+  }
+  if (mp.route == MixerRoute::kNone)
+    return fail(PSF_E_TUNING, "psf_mixer_fwd: mixer_lds=0 but only the LDS-resident kernel covers N=%lld C=%lld", (long long)N, (long long)C);
+  const WinPick& pk = mp.pk;
+  const unsigned char* images = reinterpret_cast<const unsigned char*>(workspace);
+  FwdMlpArgs fa;  // (gm and edge are window_launches')
+  fa.in = mi, fa.E = E, fa.offs = offs, fa.stream = s;
+  // (2) V0 = g(data): the matrix phase alone, on the same tiles
+  fa.V = fa.res = nullptr, fa.out = V0, fa.images = images, fa.nu = first_unit[1] - first_unit[0], fa.wg_per_cu = 0;
+  if (int rc = window_launches(tn, pk, mp.g_all_edge, B, N, L, C, N * C, false, &fa.gm, &fa.edge,
+                               [&] { return with_int<0, kMlpStepTgsMax>(pk.tgs, [&](auto t) { return launch_mixer_g<t()>(fa); }); }, "chord_mixer_g launch"))
+    return rc;
+  for (int m = 0; m < M; ++m) {  // (3) the M steps
+    fa.V = m == 0 ? V0 : out_steps[m - 1], fa.res = use_residual ? V0 : nullptr, fa.out = out_steps[m];
+    fa.images = images + (size_t)first_unit[m + 1] * kX3ImageBytes, fa.nu = first_unit[m + 2] - first_unit[m + 1];
+    fa.wg_per_cu = tn.mixer_wg_limit;
+    tn.walk_backwards = (m & 1) != 0;  // zigzag, as chain_impl
+    if (int rc = window_launches(tn, pk, pk.all_edge, B, N, L, C, N * C, false, &fa.gm, &fa.edge,
+                                 [&] { return with_int<0, kMlpStepTgsMax>(pk.tgs, [&](auto t) { return launch_fwd_mlp<t()>(L, fa); }); }, "chord_fwd_mlp launch"))
+      return rc;
+  }
+  return PSF_OK;
+}
+
+int mixer_bf16_impl(const Tuning& tn, const uint16_t* X, int64_t B, int64_t N, int32_t E, int32_t M, const uint16_t* const* A,
+                    const uint16_t* const* a, const uint16_t* const* Bw, const uint16_t* const* b, const int32_t* h, int64_t C, int32_t L,
+                    int32_t use_residual, uint16_t* V0, uint16_t* const* out_steps, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!X || !A || !a || !Bw || !b || !h || !out_steps || !workspace) return fail(PSF_E_NULL, "psf_mixer_fwd_bf16: NULL argument");
+  if (B < 0 || B > 0x7fffffff) return fail(PSF_E_SHAPE, "psf_mixer_fwd_bf16: need 0 <= B < 2^31 (got B=%lld)", (long long)B);
+  const MixerBf16Plan mp = plan_mixer_bf16(tn, N, E, M, h, C, L);
+  if (!mp.covered)
+    return fail(PSF_E_UNSUPPORTED, "psf_mixer_fwd_bf16: no kernel for N=%lld E=%d M=%d C=%lld L=%d (psf_mixer_fwd_bf16_plan): run "
+                "psf_mlp_fwd_bf16 and psf_chord_chain_fwd_bf16", (long long)N, (int)E, (int)M, (long long)C, (int)L);
+  if (!mp.run) return fail(PSF_E_UNSUPPORTED, "psf_mixer_fwd_bf16: mixer_lds=0 takes the single-launch mixer away");
+  if (!aligned_to(X, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: X must be 16-byte aligned");
+  if (V0 && !aligned_to(V0, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: V0 must be 16-byte aligned");
+  if (workspace_bytes < mp.ws_bytes || !aligned_to(workspace, 16))
+    return fail(PSF_E_SHAPE, "psf_mixer_fwd_bf16: workspace too small (psf_mixer_fwd_bf16_workspace) or not 16-byte aligned");
+  if (int rc = check_layer_tables("psf_mixer_fwd_bf16", A, a, Bw, b, M, 2)) return rc;
+  if (int rc = check_out_steps<uint16_t>("psf_mixer_fwd_bf16", out_steps, V0, M)) return rc;
+  if (B == 0) return PSF_OK;
+  int32_t O[32];
+  for (int k = 0; k <= M; ++k) O[k] = k ? L : (int32_t)C;
+  psf_mlp_bf16::Args pack;
+  if (!psf_mlp_bf16::make_plan(E, M + 1, h, O, pack.unit, &pack.U)) return fail(PSF_E_SHAPE, "psf_mixer_fwd_bf16: unit plan");
+  for (int k = 0; k < psf_mlp_bf16::kMaxK; ++k)
+    pack.m[k] = k <= M ? psf_mlp_bf16::Mlp{A[k], a[k], Bw[k], b[k], nullptr, h[k], O[k]} : psf_mlp_bf16::Mlp{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+  pack.X = X, pack.images = reinterpret_cast<unsigned char*>(workspace), pack.T = B * N, pack.E = E;
+  MixerLdsBf16Args la;
+  la.X = X, la.images = pack.images, la.V0 = V0, la.first_unit[0] = 0;
+  for (int k = 0; k <= M; ++k) la.first_unit[k + 1] = la.first_unit[k] + (h[k] + 31) / 32;
+  for (int m = 0; m < kMixerLdsBf16MaxSteps; ++m) la.out[m] = m < M ? out_steps[m] : nullptr;
+  la.store_mask = (uint32_t)chain_store_mask(out_steps, M);  // a buffer that a later step overwrites is not stored at all
+  la.M = M, la.N = (int32_t)N, la.C = (int32_t)C, la.E = E, la.L = L, la.CG = (int32_t)(C / 8), la.WS = mp.lds.WS, la.TT = (int32_t)(N / 32);
+  Offsets offs;
+  make_offsets(N, L, nullptr, &offs);
+  const hipError_t e = launch_mixer_lds_bf16(mp.lds, use_residual != 0, pack, la, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
+  return e == hipSuccess ? PSF_OK : fail_hip(e, "chord_mixer_lds<bf16> launch");
 }
 
 // psf_describe_*: argument checks, and the name of a window-kernel instance
@@ -1098,210 +1270,36 @@ int psf_chord_chain_bwd_bf16(const uint16_t* dOut, const uint16_t* const* W_step
 }
 
 int64_t psf_mixer_fwd_workspace(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
-  MixerPlan mp;
-  if (!plan_mixer(N, E, M, h, C, L, &mp)) return -1;
-  return (int64_t)mp.units * kX3ImageBytes;
+  return plan_mixer(snapshot(), 1, N, E, M, h, C, L).ws_bytes;
 }
-
 int32_t psf_mixer_fwd_plan(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
-  MixerPlan mp;
-  if (!plan_mixer(N, E, M, h, C, L, &mp)) return 0;
-  return (mp.lds_ok && g_mixer_lds.load()) ? 2 : (mp.step_ok ? 1 : 0);
+  const MixerRoute r = plan_mixer(snapshot(), 1, N, E, M, h, C, L).route;
+  return r == MixerRoute::kLds ? 2 : r == MixerRoute::kSteps ? 1 : 0;
 }
 
 int psf_mixer_fwd_in_f32(const psf_mixer_input* in, int64_t B, int64_t N, int32_t E, int32_t M, const float* const* A,
-                         const float* const* a, const float* const* Bw, const float* const* b, const int32_t* h, int64_t C,
-                         int32_t L, int32_t use_residual, float* V0, float* const* out_steps, void* workspace,
-                         int64_t workspace_bytes, void* stream) {
-  if (!in || !in->src || !A || !a || !Bw || !b || !h || !V0 || !out_steps || !workspace)
-    return fail(PSF_E_NULL, "psf_mixer_fwd: NULL argument");
-  MixerIn mi;
-  mi.src = in->src, mi.weight = in->weight, mi.bias = in->bias, mi.pos = in->pos, mi.kind = in->kind, mi.K = in->K;
-  if (in->kind == PSF_MIXER_IN_DATA) {
-    mi.weight = mi.bias = mi.pos = nullptr, mi.K = 0;
-    if (!aligned_to(in->src, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd: X must be 16-byte aligned");
-  } else if (in->kind == PSF_MIXER_IN_AFFINE) {
-    if (in->K < 1 || in->K > 3) return fail(PSF_E_SHAPE, "psf_mixer_fwd: the affine input takes 1..3 values per position (K=%d)", (int)in->K);
-    if (!in->weight) return fail(PSF_E_NULL, "psf_mixer_fwd: affine input without a weight");
-    if (!aligned_to(in->src, 4) || !aligned_to(in->weight, 4) || (in->bias && !aligned_to(in->bias, 4)))
-      return fail(PSF_E_ALIGN, "psf_mixer_fwd: affine input pointers must be 4-byte aligned");
-  } else if (in->kind == PSF_MIXER_IN_TOKENS) {
-    if (in->K < 1) return fail(PSF_E_SHAPE, "psf_mixer_fwd: empty vocabulary");
-    if (!in->weight) return fail(PSF_E_NULL, "psf_mixer_fwd: token input without a table");
-    if (!aligned_to(in->src, 8) || !aligned_to(in->weight, 16))
-      return fail(PSF_E_ALIGN, "psf_mixer_fwd: tokens must be 8-byte, the table 16-byte aligned");
-    mi.bias = nullptr;
-  } else {
-    return fail(PSF_E_SHAPE, "psf_mixer_fwd: unknown input kind %d", (int)in->kind);
-  }
-  if (mi.pos && !aligned_to(mi.pos, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd: pos must be 16-byte aligned");
-  MixerPlan mp;
-  if (!plan_mixer(N, E, M, h, C, L, &mp))
-    return fail(PSF_E_SHAPE, "psf_mixer_fwd: shape outside the fused path (N=%lld E=%d M=%d C=%lld L=%d; see psf_mixer_fwd_workspace)",
-                (long long)N, (int)E, (int)M, (long long)C, (int)L);
-  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
-  if (in->kind != PSF_MIXER_IN_DATA && !(mp.lds_ok && g_mixer_lds.load() && B <= 0x7fffffff))  // (before anything is launched)
-    return fail(PSF_E_SHAPE, "psf_mixer_fwd: an input recipe (kind %d) is evaluated by the single-launch kernel only (short sequences, "
-                "psf_mixer_fwd_plan() == 2); for N=%lld write the rows with psf_affine_rows_f32 / psf_embed_tokens_f32 and pass them",
-                (int)in->kind, (long long)N);
-  if (B == 0) return PSF_OK;
-  if (workspace_bytes < (int64_t)mp.units * kX3ImageBytes || !aligned_to(workspace, 16))
-    return fail(PSF_E_SHAPE, "psf_mixer_fwd: workspace too small (psf_mixer_fwd_workspace) or not 16-byte aligned");
-  if (!aligned_to(V0, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd: V0 must be 16-byte aligned");
-  if (B * N > (int64_t)1 << 40) return fail(PSF_E_SHAPE, "psf_mixer_fwd: B*N too large");
-  for (int k = 0; k <= M; ++k)
-    if (!A[k] || !a[k] || !Bw[k] || !b[k]) return fail(PSF_E_NULL, "psf_mixer_fwd: NULL layer pointer (MLP %d)", k);
-  for (int m = 0; m < M; ++m) {
-    if (!out_steps[m]) return fail(PSF_E_NULL, "psf_mixer_fwd: step %d: NULL output", m);
-    if (!aligned_to(out_steps[m], 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd: step %d: output not 16-byte aligned", m);
-    if (out_steps[m] == V0) return fail(PSF_E_ALIAS, "psf_mixer_fwd: step %d: out aliases V0", m);
-    if (m > 0 && out_steps[m] == out_steps[m - 1]) return fail(PSF_E_ALIAS, "psf_mixer_fwd: step %d: out aliases the step's input", m);
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  Tuning tn = snapshot();
-
-  // (1) all M + 1 weight sets -> unit images (one launch)
-  int32_t O[32], first_unit[33];
-  O[0] = (int32_t)C;
-  for (int k = 1; k <= M; ++k) O[k] = L;
-  hipError_t e = psf_x3_pack_launch(E, M + 1, A, a, Bw, b, h, O, workspace, first_unit, s);
-  if (e != hipSuccess) return fail_hip(e, "psf_mixer_fwd: pack");
-  Offsets offs;
-  make_offsets(N, L, nullptr, &offs);
-  if (mp.lds_ok && tn.mixer_lds && B <= 0x7fffffff) {  // short sequences: the whole mixer in ONE launch, V resident in LDS
-    MixerLdsArgs la;
-    la.in = mi;
-    la.images = reinterpret_cast<const unsigned char*>(workspace);
-    for (int k = 0; k <= M + 1; ++k) la.first_unit[k] = first_unit[k];
-    la.V0 = V0;
-    for (int m = 0; m < kMixerLdsMaxSteps; ++m) la.out[m] = m < M ? out_steps[m] : nullptr;
-    la.store_mask = (uint32_t)chain_store_mask(out_steps, M);  // a buffer that a later step overwrites (two-buffer inference) is not stored at all
-    la.M = M, la.N = (int32_t)N, la.C = (int32_t)C, la.E = E, la.L = L, la.CG = (int32_t)(C / 4), la.WS = mp.lds.WS;
-    la.TT = (int32_t)(N / 32), la.nu_max = mp.lds.nu_max;
-    e = launch_mixer_lds(mp.lds, use_residual != 0, la, offs, (int)B, s);
-    if (e != hipSuccess) return fail_hip(e, "chord_mixer_lds launch");
-    return PSF_OK;
-  }
-  if (!mp.step_ok)
-    return fail(PSF_E_TUNING, "psf_mixer_fwd: mixer_lds=0 but only the LDS-resident kernel covers N=%lld C=%lld", (long long)N, (long long)C);
-  // the tile geometry of every launch below
-  WinPick pk;
-  set_pick(&pk, mp.tgs, mlp_step_rows(mp.tgs), 256, mp.TR, mp.KN, N);
-  const int TG = 1 << mp.tgs;
-  // The step kernel's full-tile instance takes every row block as TR-aligned (scalar block addresses, fwd_mlp_step.h): N and
-  // every far offset multiples of TR, rows of exactly 4 TG channels, a batch element under 2^31 bytes; anything else runs the
-  // predicated instance on every tile. (ragged_in_one_launch's E: this step moves the data row, not the W row.)
-  bool blocks_aligned = (N % mp.TR) == 0 && C == 4 * (int64_t)TG && N * C * 4 < ((int64_t)1 << 31) && N * (int64_t)E * 4 < ((int64_t)1 << 31);
-  for (int k = mp.KN; k < L; ++k) blocks_aligned = blocks_aligned && (offs.v[k] % mp.TR) == 0;
-  pk.all_edge = !blocks_aligned || !tn.fwd_split || ragged_in_one_launch(tn, pk.ragged, B, N, E, C);
-  {  // (2) V0 = g(data): the matrix phase alone, on the same tiles
-    FwdMlpArgs fa;
-    fa.in = mi;
-    fa.V = fa.res = nullptr;
-    fa.out = V0;
-    fa.images = reinterpret_cast<const unsigned char*>(workspace);
-    fa.nu = first_unit[1] - first_unit[0];
-    fa.E = E;
-    fa.offs = offs;
-    fa.wg_per_cu = 0;
-    fa.stream = s;
-    const bool edge_all = pk.ragged && pk.all_edge;  // the g kernel needs its predicate only for rows >= N
-    const int rc = window_launches(tn, pk, edge_all, B, N, L, C, N * C, false, &fa.gm, &fa.edge,
-                                   [&] { return with_int<0, kMlpStepTgsMax>(mp.tgs, [&](auto t) { return launch_mixer_g<t()>(fa); }); }, "chord_mixer_g launch");
-    if (rc) return rc;
-  }
-  for (int m = 0; m < M; ++m) {  // (3) the M steps
-    FwdMlpArgs fa;
-    fa.in = mi;
-    fa.V = m == 0 ? V0 : out_steps[m - 1];
-    fa.res = use_residual ? V0 : nullptr;
-    fa.out = out_steps[m];
-    fa.images = reinterpret_cast<const unsigned char*>(workspace) + (size_t)first_unit[m + 1] * kX3ImageBytes;
-    fa.nu = first_unit[m + 2] - first_unit[m + 1];
-    fa.E = E;
-    fa.offs = offs;
-    fa.wg_per_cu = tn.mixer_wg_limit;
-    fa.stream = s;
-    tn.walk_backwards = (m & 1) != 0;  // zigzag, as chain_impl
-    const int rc = window_launches(tn, pk, pk.all_edge, B, N, L, C, N * C, false, &fa.gm, &fa.edge,
-                                   [&] { return with_int<0, kMlpStepTgsMax>(mp.tgs, [&](auto t) { return launch_fwd_mlp<t()>(L, fa); }); }, "chord_fwd_mlp launch");
-    if (rc) return rc;
-  }
-  return PSF_OK;
+                         const float* const* a, const float* const* Bw, const float* const* b, const int32_t* h, int64_t C, int32_t L,
+                         int32_t use_residual, float* V0, float* const* out_steps, void* workspace, int64_t workspace_bytes, void* stream) {
+  return mixer_impl(snapshot(), in, B, N, E, M, A, a, Bw, b, h, C, L, use_residual, V0, out_steps, workspace, workspace_bytes, stream);
 }
-
 int psf_mixer_fwd_f32(const float* X, int64_t B, int64_t N, int32_t E, int32_t M, const float* const* A,
-                      const float* const* a, const float* const* Bw, const float* const* b, const int32_t* h, int64_t C,
-                      int32_t L, int32_t use_residual, float* V0, float* const* out_steps, void* workspace,
-                      int64_t workspace_bytes, void* stream) {
-  psf_mixer_input in;
-  in.kind = PSF_MIXER_IN_DATA, in.K = 0, in.src = X, in.weight = in.bias = in.pos = nullptr;
-  return psf_mixer_fwd_in_f32(&in, B, N, E, M, A, a, Bw, b, h, C, L, use_residual, V0, out_steps, workspace, workspace_bytes, stream);
+                      const float* const* a, const float* const* Bw, const float* const* b, const int32_t* h, int64_t C, int32_t L,
+                      int32_t use_residual, float* V0, float* const* out_steps, void* workspace, int64_t workspace_bytes, void* stream) {
+  const psf_mixer_input in{PSF_MIXER_IN_DATA, 0, X, nullptr, nullptr, nullptr};
+  return mixer_impl(snapshot(), &in, B, N, E, M, A, a, Bw, b, h, C, L, use_residual, V0, out_steps, workspace, workspace_bytes, stream);
 }
 
 int32_t psf_mixer_fwd_bf16_plan(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
-  MixerLdsBf16Plan p;
-  return (g_mixer_lds.load() && plan_mixer_lds_bf16(N, E, M, h, C, L, &p)) ? 2 : 0;
+  return plan_mixer_bf16(snapshot(), N, E, M, h, C, L).run ? 2 : 0;
 }
-
 int64_t psf_mixer_fwd_bf16_workspace(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
-  MixerLdsBf16Plan p;
-  if (!plan_mixer_lds_bf16(N, E, M, h, C, L, &p)) return -1;
-  return (int64_t)p.units * psf_mlp_bf16::kImgBytes;
+  return plan_mixer_bf16(snapshot(), N, E, M, h, C, L).ws_bytes;
 }
 
 int psf_mixer_fwd_bf16(const uint16_t* X, int64_t B, int64_t N, int32_t E, int32_t M, const uint16_t* const* A,
-                       const uint16_t* const* a, const uint16_t* const* Bw, const uint16_t* const* b, const int32_t* h, int64_t C,
-                       int32_t L, int32_t use_residual, uint16_t* V0, uint16_t* const* out_steps, void* workspace,
-                       int64_t workspace_bytes, void* stream) {
-  if (!X || !A || !a || !Bw || !b || !h || !out_steps || !workspace) return fail(PSF_E_NULL, "psf_mixer_fwd_bf16: NULL argument");
-  if (B < 0 || B > 0x7fffffff) return fail(PSF_E_SHAPE, "psf_mixer_fwd_bf16: need 0 <= B < 2^31 (got B=%lld)", (long long)B);
-  MixerLdsBf16Plan mp;
-  if (!plan_mixer_lds_bf16(N, E, M, h, C, L, &mp))
-    return fail(PSF_E_UNSUPPORTED, "psf_mixer_fwd_bf16: no kernel for N=%lld E=%d M=%d C=%lld L=%d (psf_mixer_fwd_bf16_plan): run "
-                "psf_mlp_fwd_bf16 and psf_chord_chain_fwd_bf16", (long long)N, (int)E, (int)M, (long long)C, (int)L);
-  if (!g_mixer_lds.load()) return fail(PSF_E_UNSUPPORTED, "psf_mixer_fwd_bf16: mixer_lds=0 takes the single-launch mixer away");
-  if (!aligned_to(X, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: X must be 16-byte aligned");
-  if (V0 && !aligned_to(V0, 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: V0 must be 16-byte aligned");
-  if (workspace_bytes < (int64_t)mp.units * psf_mlp_bf16::kImgBytes || !aligned_to(workspace, 16))
-    return fail(PSF_E_SHAPE, "psf_mixer_fwd_bf16: workspace too small (psf_mixer_fwd_bf16_workspace) or not 16-byte aligned");
-  for (int k = 0; k <= M; ++k) {
-    if (!A[k] || !a[k] || !Bw[k] || !b[k]) return fail(PSF_E_NULL, "psf_mixer_fwd_bf16: NULL layer pointer (MLP %d)", k);
-    if (!aligned_to(A[k], 2) || !aligned_to(a[k], 2) || !aligned_to(Bw[k], 2) || !aligned_to(b[k], 2))
-      return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: weights and biases must be 2-byte aligned (MLP %d)", k);
-  }
-  for (int m = 0; m < M; ++m) {
-    if (!out_steps[m]) return fail(PSF_E_NULL, "psf_mixer_fwd_bf16: step %d: NULL output", m);
-    if (!aligned_to(out_steps[m], 16)) return fail(PSF_E_ALIGN, "psf_mixer_fwd_bf16: step %d: output not 16-byte aligned", m);
-    if (out_steps[m] == V0) return fail(PSF_E_ALIAS, "psf_mixer_fwd_bf16: step %d: out aliases V0", m);
-    if (m > 0 && out_steps[m] == out_steps[m - 1]) return fail(PSF_E_ALIAS, "psf_mixer_fwd_bf16: step %d: out aliases the step's input", m);
-  }
-  if (B == 0) return PSF_OK;
-
-  int32_t O[32];
-  O[0] = (int32_t)C;
-  for (int k = 1; k <= M; ++k) O[k] = L;
-  psf_mlp_bf16::Args pack;
-  if (!psf_mlp_bf16::make_plan(E, M + 1, h, O, pack.unit, &pack.U)) return fail(PSF_E_SHAPE, "psf_mixer_fwd_bf16: unit plan");
-  for (int k = 0; k < psf_mlp_bf16::kMaxK; ++k)
-    pack.m[k] = k <= M ? psf_mlp_bf16::Mlp{A[k], a[k], Bw[k], b[k], nullptr, h[k], O[k]} : psf_mlp_bf16::Mlp{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
-  pack.X = X;
-  pack.images = reinterpret_cast<unsigned char*>(workspace);
-  pack.T = B * N;
-  pack.E = E;
-  MixerLdsBf16Args la;
-  la.X = X;
-  la.images = pack.images;
-  la.first_unit[0] = 0;
-  for (int k = 0; k <= M; ++k) la.first_unit[k + 1] = la.first_unit[k] + (h[k] + 31) / 32;
-  la.V0 = V0;
-  for (int m = 0; m < kMixerLdsBf16MaxSteps; ++m) la.out[m] = m < M ? out_steps[m] : nullptr;
-  la.store_mask = (uint32_t)chain_store_mask(out_steps, M);  // a buffer that a later step overwrites is not stored at all
-  la.M = M, la.N = (int32_t)N, la.C = (int32_t)C, la.E = E, la.L = L, la.CG = (int32_t)(C / 8), la.WS = mp.WS, la.TT = (int32_t)(N / 32);
-  Offsets offs;
-  make_offsets(N, L, nullptr, &offs);
-  const hipError_t e = launch_mixer_lds_bf16(mp, use_residual != 0, pack, la, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
-  return e == hipSuccess ? PSF_OK : fail_hip(e, "chord_mixer_lds<bf16> launch");
+                       const uint16_t* const* a, const uint16_t* const* Bw, const uint16_t* const* b, const int32_t* h, int64_t C, int32_t L,
+                       int32_t use_residual, uint16_t* V0, uint16_t* const* out_steps, void* workspace, int64_t workspace_bytes, void* stream) {
+  return mixer_bf16_impl(snapshot(), X, B, N, E, M, A, a, Bw, b, h, C, L, use_residual, V0, out_steps, workspace, workspace_bytes, stream);
 }
 
 int psf_set_tuning(const char* key, int32_t value) {

@@ -120,14 +120,15 @@ def _block_sizes(E: int, g: nn.Module, fs: Sequence[nn.Module]):
     return None if found is None else found[0]
 
 
-def _route_ok(N: int, E: int, M: int, C: int, L: int, h, tokens: int = 1 << 62) -> bool:
+def _route_ok(N: int, E: int, M: int, C: int, L: int, h, tokens: int = 1 << 62, plan=None) -> bool:
     if route != "auto":
         return route == "always"
     if N >= 8192 and C <= 32 and max(h) <= 32:  # (32-channel rows since the step kernel's diet: genome shape 488 -> 451 us)
         return True
     # short sequences: ONE launch with V resident in LDS (csrc/mixer_lds.h) against producer + chain
     # (profiles/r04n_mixer_bench_short.log: cfg1 115 -> 89 us per forward, N = 512: 134 -> 106)
-    plan = _lib.load().psf_mixer_fwd_plan(N, E, M, h, C, L)
+    if plan is None:  # (``_found`` passes the answer it already has)
+        plan = _lib.load().psf_mixer_fwd_plan(N, E, M, h, C, L)
     if plan == 2:
         return True
     # An EAGER forward of a small network is bound by the host, and the fused route is one library call for all its M + 2
@@ -141,72 +142,57 @@ def _route_ok(N: int, E: int, M: int, C: int, L: int, h, tokens: int = 1 << 62) 
     return False
 
 
+class _Found(tuple):
+    """``found``: ((M, h table, C, L), [(lin1, lin2), ...]), as ever, carrying the library's two answers for the shape: ``plan``
+    (psf_mixer_fwd_plan / psf_mixer_fwd_bf16_plan) and ``ws_bytes``. The forward that is handed one asks neither again."""
+
+
+def _found(N: int, E: int, g: nn.Module, fs: Sequence[nn.Module], dtype: torch.dtype, tokens=None):
+    """``found`` of either dtype from ONE walk of the blocks, one plan and one workspace query; None when blocks or shape are not covered
+    (f32: psf_mixer_fwd_workspace < 0; bf16: psf_mixer_fwd_bf16_plan != 2) or, f32 with ``tokens`` (B N) given, ``_route_ok`` says no."""
+    bp = _block_pairs(E, g, fs, dtype)
+    if bp is None:
+        return None
+    M, h, C, L = bp[0]
+    lib, bf = _lib.load(), dtype == torch.bfloat16
+    plan = (lib.psf_mixer_fwd_bf16_plan if bf else lib.psf_mixer_fwd_plan)(N, E, M, h, C, L)
+    if (plan != 2) if bf else (tokens is not None and not _route_ok(N, E, M, C, L, h, tokens, plan)):
+        return None
+    ws_bytes = (lib.psf_mixer_fwd_bf16_workspace if bf else lib.psf_mixer_fwd_workspace)(N, E, M, h, C, L)
+    if ws_bytes < 0:
+        return None
+    found = _Found(bp)
+    found.plan, found.ws_bytes = plan, ws_bytes
+    return found
+
+
+def _covered(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module], dtype: torch.dtype):
+    """``found`` for ``data`` [B, N, E] of ``dtype`` on the GPU inside the dtype's limits, whatever the route switches say; or None."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or not x.is_cuda or x.dtype != dtype:
+        return None
+    return _found(x.shape[1], x.shape[-1], g, fs, dtype)
+
+
 def find(r: Recipe, g: nn.Module, fs: Sequence[nn.Module]):
     """((M, h table, C, L), [(lin1, lin2), ...]) when the fused mixer can run from this recipe, nothing needs a gradient and
-    ``route`` wants it; None otherwise. ``mixer_forward_in`` takes it as ``found`` and does not walk the blocks again."""
-    if not enabled or not r.ok() or torch.is_grad_enabled() and any(t.requires_grad for t in r.tensors() if t.is_floating_point()):
+    ``route`` wants it; None otherwise. ``mixer_forward_in`` takes it as ``found`` and neither walks the blocks nor asks the library again."""
+    if not enabled or route == "never" or not r.ok() or torch.is_grad_enabled() and (
+            any(t.requires_grad for t in r.tensors() if t.is_floating_point()) or any(p.requires_grad for b in (g, *fs) for p in b.parameters())):
         return None
-    if _needs_grad(torch.empty(0), [g, *fs]):
+    return _found(r.N, r.E, g, fs, torch.float32, r.B * r.N)
+
+
+def find_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]):
+    """``found`` for ``mixer_forward_bf16`` when ``bf16_route`` wants the single launch, it covers the call and nothing needs a
+    gradient; None otherwise."""
+    if not enabled or bf16_route != "always" or _needs_grad(x, [g, *fs]):
         return None
-    found = _block_pairs(r.E, g, fs)
-    if found is None:
-        return None
-    M, h, C, L = found[0]
-    if _route_ok(r.N, r.E, M, C, L, h, r.B * r.N) and _lib.load().psf_mixer_fwd_workspace(r.N, r.E, M, h, C, L) >= 0:
-        return found
-    return None
+    return _covered(x, g, fs, torch.bfloat16)
 
 
 def eligible_recipe(r: Recipe, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
     """The fused mixer can run from this recipe, nothing needs a gradient, and ``route`` wants it."""
     return find(r, g, fs) is not None
-
-
-def mixer_forward_in(r: Recipe, g: nn.Module, fs: Sequence[nn.Module], use_residual: bool, found=None) -> torch.Tensor:
-    """V_M [B, N, C] from the recipe of ``data``. ``found``: what ``find`` returned for these arguments; without it the caller
-    checks ``eligible_recipe`` (or ``covered``) first."""
-    if found is None:
-        found = _block_pairs(r.E, g, fs)
-        if found is None:
-            raise ValueError("psf_mixer_fwd does not cover these blocks: every block must be Linear(E, h) -> GELU(erf) -> "
-                             "Linear(h, out) in f32 on input width E, the link MLPs agreeing on L (check eligible() / covered())")
-    (M, h, C, L), pairs = found
-    B, N, E = r.B, r.N, r.E
-    dev = r.src.device
-    lib = _lib.load()
-    if r.kind != _lib.MIXER_IN_DATA and not (recipe_in_kernel and lib.psf_mixer_fwd_plan(N, E, M, h, C, L) == 2):
-        r = Recipe.data(r.rows())  # the per-step kernels take rows (psf_mixer_fwd_plan: 2 = the single-launch kernel runs)
-
-    def prep(t, align):
-        if t is None:
-            return None
-        t = t.detach().contiguous()
-        return t if t.data_ptr() % align == 0 else t.clone()
-
-    keep = [prep(r.src, 16 if r.kind == _lib.MIXER_IN_DATA else 8), prep(r.weight, 16), prep(r.bias, 4), prep(r.pos, 16)]
-    spec = _lib.MixerInput(r.kind, int(r.K), *[t.data_ptr() if t is not None else None for t in keep])
-    params = [p if p.is_contiguous() else p.contiguous() for l1, l2 in pairs for p in (l1.weight, l1.bias, l2.weight, l2.bias)]
-    ws_bytes = lib.psf_mixer_fwd_workspace(N, E, M, h, C, L)
-    if ws_bytes < 0:
-        raise ValueError("psf_mixer_fwd does not cover this shape")
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
-    V0 = torch.empty((B, N, C), dtype=torch.float32, device=dev)
-    bufs = [torch.empty_like(V0) for _ in range(min(M, 2))]
-    o_tab = (ctypes.c_void_p * M)(*[bufs[m % len(bufs)].data_ptr() for m in range(M)])
-    with torch.cuda.device(dev):
-        rc = lib.psf_mixer_fwd_in_f32(ctypes.byref(spec), B, N, E, M, _ptrs(params[0::4]), _ptrs(params[1::4]), _ptrs(params[2::4]),
-                                      _ptrs(params[3::4]), h, C, L, 1 if use_residual else 0, V0.data_ptr(), o_tab, ws.data_ptr(),
-                                      ws_bytes, _lib.stream_ptr(dev))
-    _lib.check(rc, "psf_mixer_fwd_in_f32")
-    return bufs[(M - 1) % len(bufs)]
-
-
-def _sizes(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]):
-    """(N, E, M, h table, C, L) for ``data`` given as a tensor, or None."""
-    if x.dim() != 3:
-        return None
-    sz = _block_sizes(x.shape[-1], g, fs)
-    return None if sz is None else (x.shape[1], x.shape[-1], *sz)
 
 
 def eligible(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
@@ -215,8 +201,53 @@ def eligible(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
 
 def covered(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
     """The shape is inside the fused path's limits (whatever ``route`` says about using it)."""
-    sz = _sizes(x, g, fs)
-    return sz is not None and x.is_cuda and x.dtype == torch.float32 and _lib.load().psf_mixer_fwd_workspace(*sz) >= 0
+    return _covered(x, g, fs, torch.float32) is not None
+
+
+def covered_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
+    """bf16 ``data`` [B, N, E] on the GPU, every block Linear -> GELU(erf) -> Linear in bf16, the link MLPs agreeing on L, and a
+    shape the single launch takes (psf_mixer_fwd_bf16_plan == 2) — whatever ``bf16_route`` says about using it."""
+    return _covered(x, g, fs, torch.bfloat16) is not None
+
+
+def _launch(entry: str, first, shape, found, use_residual: bool, dtype: torch.dtype, dev, with_v0: bool) -> torch.Tensor:
+    """What both forwards end in: the four parameter tables, the workspace, (f32: the buffer that receives g(data);) two ping-pong
+    step buffers, the output table, the call of ``entry`` with ``first`` as its first argument, the check. Returns V_M."""
+    ((M, h, C, L), pairs), (B, N, E) = found, shape
+    params = [p if p.is_contiguous() else p.contiguous() for l1, l2 in pairs for p in (l1.weight, l1.bias, l2.weight, l2.bias)]
+    ws = torch.empty(found.ws_bytes, dtype=torch.uint8, device=dev)
+    V0 = torch.empty((B, N, C), dtype=dtype, device=dev)  # (bf16, whose entry takes none: a step buffer; empty_like is the cheaper call)
+    bufs = [torch.empty_like(V0) for _ in range(min(M, 2))] if with_v0 else [V0, torch.empty_like(V0)][:M]
+    o_tab = (ctypes.c_void_p * M)(*[bufs[m % len(bufs)].data_ptr() for m in range(M)])
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.load(), entry)(first, B, N, E, M, _ptrs(params[0::4]), _ptrs(params[1::4]), _ptrs(params[2::4]),
+                                         _ptrs(params[3::4]), h, C, L, 1 if use_residual else 0, V0.data_ptr() if with_v0 else None,
+                                         o_tab, ws.data_ptr(), found.ws_bytes, _lib.stream_ptr(dev))
+    _lib.check(rc, entry)
+    return bufs[(M - 1) % len(bufs)]
+
+
+def _aligned(t, align):  # ``t`` detached, contiguous and ``align``-byte aligned (a copy where it is not); None stays None
+    if t is not None:
+        t = t.detach().contiguous()
+        return t if t.data_ptr() % align == 0 else t.clone()
+
+
+def mixer_forward_in(r: Recipe, g: nn.Module, fs: Sequence[nn.Module], use_residual: bool, found=None) -> torch.Tensor:
+    """V_M [B, N, C] from the recipe of ``data``. ``found``: what ``find`` returned for these arguments; without it the caller
+    checks ``eligible_recipe`` (or ``covered``) first."""
+    if found is None:
+        found = _found(r.N, r.E, g, fs, torch.float32)
+        if found is None:
+            raise ValueError("psf_mixer_fwd does not cover this shape" if _block_pairs(r.E, g, fs) is not None else
+                             "psf_mixer_fwd does not cover these blocks: every block must be Linear(E, h) -> GELU(erf) -> "
+                             "Linear(h, out) in f32 on input width E, the link MLPs agreeing on L (check eligible() / covered())")
+    shape, dev = (r.B, r.N, r.E), r.src.device
+    if r.kind != _lib.MIXER_IN_DATA and not (recipe_in_kernel and found.plan == 2):
+        r = Recipe.data(r.rows())  # the per-step kernels take rows (psf_mixer_fwd_plan: 2 = the single-launch kernel runs)
+    keep = [_aligned(r.src, 16 if r.kind == _lib.MIXER_IN_DATA else 8), _aligned(r.weight, 16), _aligned(r.bias, 4), _aligned(r.pos, 16)]
+    spec = _lib.MixerInput(r.kind, int(r.K), *[t.data_ptr() if t is not None else None for t in keep])
+    return _launch("psf_mixer_fwd_in_f32", ctypes.byref(spec), shape, found, use_residual, torch.float32, dev, True)
 
 
 def mixer_forward(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module], use_residual: bool) -> torch.Tensor:
@@ -224,57 +255,24 @@ def mixer_forward(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module], use_re
     return mixer_forward_in(Recipe.data(x), g, fs, use_residual)
 
 
-# ---------------------------------------------------------------------------------------------------
-# bf16: the single-launch mixer of short sequences (psf_mixer_fwd_bf16)
-# ---------------------------------------------------------------------------------------------------
-def _found_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]):
-    """What ``_block_pairs`` finds for bf16 ``data`` [B, N, E] on the GPU that psf_mixer_fwd_bf16 covers, or None."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 3 or not x.is_cuda or x.dtype != torch.bfloat16:
-        return None
-    found = _block_pairs(x.shape[-1], g, fs, torch.bfloat16)
-    if found is None:
-        return None
-    M, h, C, L = found[0]
-    return found if _lib.load().psf_mixer_fwd_bf16_plan(x.shape[1], x.shape[-1], M, h, C, L) == 2 else None
-
-
-def covered_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]) -> bool:
-    """bf16 ``data`` [B, N, E] on the GPU, every block Linear -> GELU(erf) -> Linear in bf16, the link MLPs agreeing on L, and a
-    shape the single launch takes (psf_mixer_fwd_bf16_plan == 2) — whatever ``bf16_route`` says about using it."""
-    return _found_bf16(x, g, fs) is not None
-
-
-def find_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module]):
-    """``found`` for ``mixer_forward_bf16`` when ``bf16_route`` wants the single launch, it covers the call and nothing needs a
-    gradient; None otherwise."""
-    if not enabled or bf16_route != "always" or _needs_grad(x, [g, *fs]):
-        return None
-    return _found_bf16(x, g, fs)
-
-
 def mixer_forward_bf16(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module], use_residual: bool, found=None) -> torch.Tensor:
-    """V_M [B, N, C] in bf16 from bf16 ``data`` [B, N, E]: the bits of ``fused_mlp_forward_bf16`` + ``chord_chain``. Two ping-pong
-    step buffers, as ``mixer_forward_in``. Caller checks ``covered_bf16`` (or passes what ``find_bf16`` returned)."""
+    """V_M [B, N, C] in bf16 from bf16 ``data`` [B, N, E] in ONE launch (psf_mixer_fwd_bf16): the bits of ``fused_mlp_forward_bf16``
+    + ``chord_chain``. Caller checks ``covered_bf16`` (or passes what ``find_bf16`` returned)."""
     if found is None:
-        found = _found_bf16(x, g, fs)
+        found = _covered(x, g, fs, torch.bfloat16)
         if found is None:
             raise ValueError("psf_mixer_fwd_bf16 does not cover this call: bf16 data [B, N, E] on the GPU, every block "
                              "Linear(E, h) -> GELU(erf) -> Linear(h, out) in bf16, the link MLPs agreeing on L (check covered_bf16())")
-    (M, h, C, L), pairs = found
-    B, N, E = x.shape
-    dev = x.device
-    lib = _lib.load()
-    x = x.detach().contiguous()
-    if x.data_ptr() % 16:
-        x = x.clone()
-    params = [p.detach().contiguous() for l1, l2 in pairs for p in (l1.weight, l1.bias, l2.weight, l2.bias)]
-    ws_bytes = lib.psf_mixer_fwd_bf16_workspace(N, E, M, h, C, L)
-    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
-    bufs = [torch.empty((B, N, C), dtype=torch.bfloat16, device=dev) for _ in range(min(M, 2))]
-    o_tab = (ctypes.c_void_p * M)(*[bufs[m % len(bufs)].data_ptr() for m in range(M)])
-    with torch.cuda.device(dev):
-        rc = lib.psf_mixer_fwd_bf16(x.data_ptr(), B, N, E, M, _ptrs(params[0::4]), _ptrs(params[1::4]), _ptrs(params[2::4]),
-                                    _ptrs(params[3::4]), h, C, L, 1 if use_residual else 0, None, o_tab, ws.data_ptr(), ws.numel(),
-                                    _lib.stream_ptr(dev))
-    _lib.check(rc, "psf_mixer_fwd_bf16")
-    return bufs[(M - 1) % len(bufs)]
+    x = _aligned(x, 16)
+    return _launch("psf_mixer_fwd_bf16", x.data_ptr(), tuple(x.shape), found, use_residual, torch.bfloat16, x.device, False)
+
+
+def forward_from_data(x: torch.Tensor, g: nn.Module, fs: Sequence[nn.Module], use_residual: bool):
+    """V_M from ``data`` [B, N, E] by the fused mixer of its dtype — bf16: the single launch where ``bf16_route`` wants it; otherwise
+    the f32 mixer unless ``data`` itself requires a gradient — or None when that mixer does not take the call."""
+    if x.dtype == torch.bfloat16:
+        found = find_bf16(x, g, fs)
+        return None if found is None else mixer_forward_bf16(x, g, fs, use_residual, found)
+    r = Recipe.data(x)
+    found = None if x.requires_grad else find(r, g, fs)
+    return None if found is None else mixer_forward_in(r, g, fs, use_residual, found)

@@ -194,11 +194,7 @@ class _ChordMixer(nn.Module):
         """V_M straight from ``data`` with every W_m computed inside its chain step and never written (fused_mixer.py,
         csrc/fwd_mlp_step.h) — psf.py:165-188 in M + 2 launches. None when that path does not apply (a gradient is
         needed, shapes outside its limits): the caller then runs ``produce`` + ``mix``."""
-        if data.dtype == torch.bfloat16:  # a bf16 model: the single-launch mixer of short sequences, where fused_mixer.bf16_route wants it
-            fs = list(self.fs)
-            found = fused_mixer.find_bf16(data, self.g, fs) if self.fused_chain else None
-            return None if found is None else fused_mixer.mixer_forward_bf16(data, self.g, fs, use_residuals, found)
-        return None if data.requires_grad else self.mix_from_recipe(fused_mixer.Recipe.data(data), use_residuals)
+        return fused_mixer.forward_from_data(data, self.g, list(self.fs), use_residuals) if self.fused_chain else None
 
     def mix(self, data: torch.Tensor, V: torch.Tensor, use_residuals: bool, links=None) -> torch.Tensor:
         """The hot loop of PSFNet.forward (SyntheticExperiments/psf.py:167-188). ``links`` may carry

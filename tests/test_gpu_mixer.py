@@ -393,3 +393,41 @@ def test_same_samples_on_both_sides_of_the_route_boundary_and_under_capture(gpu)
     assert float((large[:32].double() - ref).abs().max()) <= 2e-5 * scale
     assert float((captured.double() - ref).abs().max()) <= 2e-5 * scale
     assert torch.equal(captured, large[:32])  # both W-through-memory: the same kernels on the same rows, the same bits
+
+
+def test_an_eager_forward_asks_the_library_once_for_the_plan_and_once_for_the_workspace(gpu, monkeypatch):
+    """``find`` / ``find_bf16`` hand the forward everything the library said about the shape: from ``find`` through the launch an
+    eager no-grad forward makes at most ONE plan query and ONE workspace query (psf_mixer_fwd_plan / _workspace and their bf16
+    twins, counted here on the loaded library), whichever kernels run — the single launch (512 x 8), the per-step kernels on
+    ragged tiles (600 x 12), a token recipe evaluated inside the single-launch kernel (128 x 8), the bf16 single launch
+    (128 x 8) — and the result has the bits of the same forward called without ``found``."""
+    from sparsefactorization_amd import _lib, fused_mixer
+    lib, asked = _lib.load(), []
+    for name in ("psf_mixer_fwd_plan", "psf_mixer_fwd_workspace", "psf_mixer_fwd_bf16_plan", "psf_mixer_fwd_bf16_workspace"):
+        monkeypatch.setattr(lib, name, lambda *a, _real=getattr(lib, name), _name=name: (asked.append(_name), _real(*a))[1])
+    monkeypatch.setattr(fused_mixer, "route", "always")
+    monkeypatch.setattr(fused_mixer, "bf16_route", "always")
+    monkeypatch.setattr(fused_mixer, "recipe_in_kernel", True)
+    gen = torch.Generator().manual_seed(13)
+
+    def blocks(E, h, C, L, M, dtype=torch.float32):
+        g, fs = _blocks(E, h, C, L, M, seed=4)
+        return g.to(gpu, dtype), [f.to(gpu, dtype) for f in fs]
+    data = lambda x: (fused_mixer.find, fused_mixer.mixer_forward_in, fused_mixer.Recipe.data(x.to(gpu)))  # noqa: E731
+    tokens = fused_mixer.Recipe.tokens(torch.randint(0, 6, (3, 128), generator=gen).to(gpu), torch.randn(6, 32, generator=gen).to(gpu),
+                                       torch.randn(128, 32, generator=gen).to(gpu))
+    cases = [("data 512 x 8", *data(torch.randn(2, 512, 32, generator=gen)), *blocks(32, 32, 8, 10, 9)),
+             ("data 600 x 12", *data(torch.randn(2, 600, 12, generator=gen)), *blocks(12, 40, 12, 9, 5)),
+             ("tokens 128 x 8", fused_mixer.find, fused_mixer.mixer_forward_in, tokens, *blocks(32, 32, 8, 8, 7)),
+             ("bf16 128 x 8", fused_mixer.find_bf16, fused_mixer.mixer_forward_bf16, torch.randn(3, 128, 32, generator=gen).to(gpu, torch.bfloat16),
+              *blocks(32, 32, 8, 8, 7, torch.bfloat16))]
+    with torch.no_grad():
+        for name, find, forward, x, g, fs in cases:
+            del asked[:]
+            found = find(x, g, fs)
+            assert found is not None, name
+            got = forward(x, g, fs, True, found)
+            torch.cuda.synchronize()
+            print(name, asked)
+            assert sum(a.endswith("_plan") for a in asked) <= 1 and sum(a.endswith("_workspace") for a in asked) <= 1, (name, asked)
+            assert torch.isfinite(got.float()).all() and torch.equal(got, forward(x, g, fs, True)), name
