@@ -162,6 +162,13 @@ def test_mixer_from_the_recipe_of_data_matches_the_float64_reference(gpu, name, 
     assert np.isfinite(got).all()
     assert rel_inf(got, want) <= TOL, f"{name}: rel {rel_inf(got, want):.3e}"
     assert rel_inf(got_k, want) <= TOL, f"{name} (recipe in the kernel): rel {rel_inf(got_k, want):.3e}"
+    from sparsefactorization_amd import _lib
+    single_launch = _lib.load().psf_mixer_fwd_plan(N, E, *fused_mixer._block_sizes(E, g, fs)) == 2
+    assert single_launch == name.endswith("_lds")
+    if single_launch:
+        # the single launch evaluated the recipe itself: the rows psf_affine_rows_f32 / psf_embed_tokens_f32 wrote for `got` and
+        # the rows it computed are the same bits (include/psf_chord.h), and so is everything after them
+        assert np.array_equal(got, got_k), f"{name}: rows written once and rows from the recipe differ"
 
 
 @pytest.mark.parametrize("K,E,bias", [(2, 32, True), (1, 8, True), (3, 12, False)])
