@@ -381,8 +381,8 @@ int psf_mlp_fwd_f32(const float* X, int64_t T, int32_t E, int32_t K, const float
  *   16-byte aligned (PSF_E_ALIGN), weights and biases 2-byte aligned. Nothing outside Y[k][0 .. T*O[k]) is written, for odd
  *   O[k] and ragged T too. `workspace`: caller-owned, 16-byte-aligned device scratch of at least
  *   psf_mlp_fwd_bf16_workspace(E, K, h, O) bytes (6912 per 32 hidden rows of each MLP; -1: unsupported sizes). No allocation,
- *   no synchronisation; capturable in a HIP graph. Wider layers (E >= 128, O = 128: the LRA networks), training and the
- *   backward are not covered.
+ *   no synchronisation; capturable in a HIP graph. Wider layers (E >= 128, O = 128: the LRA networks) are not covered; the
+ *   backward is psf_mlp_bwd_bf16 (E <= 32).
  */
 int64_t psf_mlp_fwd_bf16_workspace(int32_t E, int32_t K, const int32_t* h, const int32_t* O);
 int psf_mlp_fwd_bf16(const uint16_t* X, int64_t T, int32_t E, int32_t K, const uint16_t* const* A, const uint16_t* const* a,
@@ -497,6 +497,37 @@ int psf_mlp_bwd_f32(const float* X, int64_t T, int32_t E, int32_t K, const float
                     const float* const* B, const int32_t* h, const int32_t* O, const float* const* dY, float* dX,
                     float* const* dA, float* const* da, float* const* dB, float* const* db, void* workspace,
                     int64_t workspace_bytes, void* stream);
+
+/*
+ * The same backward for a bf16 model (raw bits), csrc/mlp_bwd_bf16.hip: table conventions, validation order and error codes as
+ * psf_mlp_bwd_f32 and psf_mlp_fwd_bf16. Added without a version change (additive). The forward is psf_mlp_fwd_bf16, which
+ * saves nothing: the hidden layer is recomputed here with the forward's bits.
+ * Arithmetic — the sequence of roundings that PyTorch's bf16 autograd produces for nn.Linear -> nn.GELU() -> nn.Linear with
+ * the first layers stacked: one rounding per tensor it materialises, f32 accumulation inside each GEMM and each sum. For
+ * each MLP k, with z and hh exactly as in psf_mlp_fwd_bf16's contract (z = bf16_rne(f32(X A^T + a)), hh = bf16_rne(GELU_f32(z))):
+ *     g[t,j]  = bf16_rne( f32( sum_o dY[t,o] * B[o,j] ) )
+ *     d[t,j]  = bf16_rne( f32(g[t,j]) * GELU'_f32(z[t,j]) )      GELU' = Phi + z phi, Phi evaluated to 7.5e-8 absolute
+ *     dA[j,e] = bf16_rne( f32( sum_t d[t,j] * X[t,e] ) )          da[j] = bf16_rne( f32( sum_t d[t,j] ) )
+ *     dB[o,j] = bf16_rne( f32( sum_t dY[t,o] * hh[t,j] ) )        db[o] = bf16_rne( f32( sum_t dY[t,o] ) )
+ *     dX[t,e] = bf16_rne( f32( sum_k sum_j d_k[t,j] * A_k[j,e] ) )       ONE rounding over all K MLPs
+ *   Products of bf16 values are exact in f32; the sums are in f32, in an order that is unspecified but fixed: weight gradients
+ *   are reduced in a fixed order without float atomics, so two calls on the same inputs give the same bits. A NaN stays a NaN.
+ *   dX[t,:] depends on token t's rows of X and dY only. Every gradient tensor is fully overwritten; nothing outside the
+ *   gradient tensors and the workspace is written; nothing at or beyond X + T*E or dY[k] + T*O[k] is read, for odd O[k] and
+ *   ragged T too. dX may be NULL (not computed).
+ *   Limits: E a multiple of 8, 8 <= E <= 32; 1 <= h[k] <= 128; 1 <= O[k] <= 32; 1 <= K <= 32; T >= 1; X, dX and every dY[k]
+ *   16-byte aligned (PSF_E_ALIGN), weights, biases and their gradients 2-byte aligned. `workspace`: caller-owned,
+ *   16-byte-aligned device scratch of at least psf_mlp_bwd_bf16_workspace(T, E, K, h, O) bytes (packed weight images, one f32
+ *   partial-sum slot per workgroup, the reduction's stage; -1: unsupported sizes).
+ *   Validation, before any HIP call and in this order: NULL tables (PSF_E_NULL); shape (PSF_E_SHAPE); X, dX, dY[k] alignment
+ *   (PSF_E_ALIGN); workspace too small or misaligned (PSF_E_SHAPE); per MLP NULL / 2-byte alignment.
+ *   No allocation, no synchronisation; capturable in a HIP graph.
+ */
+int64_t psf_mlp_bwd_bf16_workspace(int64_t T, int32_t E, int32_t K, const int32_t* h, const int32_t* O);
+int psf_mlp_bwd_bf16(const uint16_t* X, int64_t T, int32_t E, int32_t K, const uint16_t* const* A, const uint16_t* const* a,
+                     const uint16_t* const* B, const int32_t* h, const int32_t* O, const uint16_t* const* dY, uint16_t* dX,
+                     uint16_t* const* dA, uint16_t* const* da, uint16_t* const* dB, uint16_t* const* db, void* workspace,
+                     int64_t workspace_bytes, void* stream);
 
 /*
  * Producer side at the WIDE (LRA) sizes — the same K MLPs for E up to 1024 and outputs up to 128: reference ListOps

@@ -29,7 +29,7 @@ HEADERS = ["psf_common.h", "fwd_kernels.h", "fwd_window.h", "fwd_window_launch.h
            "bwd_window.h", "bwd_dw_chunk.h", "bwd_window_launch.h", "bwd_fused.h", "bwd_fused_bf16.h", "fwd_chain_lds.h", "fwd_chain_lds_bf16.h", "fwd_chain_lds_launch.h", "bwd_chain_lds.h", "fwd_mlp_step.h", "fwd_mlp_step_launch.h", "mixer_lds.h", "mixer_lds_launch.h", "mixer_lds_bf16.h", "mixer_lds_bf16_launch.h", "mlp_x3_image.h", "mlp_bf16_image.h", "mlp_bf16_tile.h", "mlp_fwd_x3.h", "mlp_x3_common.h", "mlp_planes.h", "x3_gemm.h",
            os.path.join("..", "..", "include", "psf_chord.h"), os.path.join("..", "..", "include", "psf_chord_tuning.h")]
 SOURCES = ["psf_chord.hip", "fwd_window_inst.hip", "bwd_window_inst.hip", "bwd_fused_bf16_inst.hip", "linear_wgrad.hip",
-           "fwd_chain_lds_inst.hip", "fwd_chain_lds_bf16_inst.hip", "bwd_chain_lds_inst.hip", "fwd_mlp_step_inst.hip", "mixer_lds_inst.hip", "mixer_lds_bf16_inst.hip", "embed.hip", "flat_head.hip", "sum_tensors.hip", "adam.hip", "mlp_fwd.hip", "mlp_fwd_x3.hip", "mlp_fwd_bf16.hip", "mlp_bwd.hip", "mlp_wide.hip", "stream_mix.hip"]
+           "fwd_chain_lds_inst.hip", "fwd_chain_lds_bf16_inst.hip", "bwd_chain_lds_inst.hip", "fwd_mlp_step_inst.hip", "mixer_lds_inst.hip", "mixer_lds_bf16_inst.hip", "embed.hip", "flat_head.hip", "sum_tensors.hip", "adam.hip", "mlp_fwd.hip", "mlp_fwd_x3.hip", "mlp_fwd_bf16.hip", "mlp_bwd.hip", "mlp_bwd_bf16.hip", "mlp_wide.hip", "stream_mix.hip"]
 
 # -ffp-contract=off: products and sums stay separate roundings (bitwise parity with the CPU oracle).
 HIPCC_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
@@ -98,6 +98,9 @@ def _unit_table():
              # -fno-slp-vectorize: keeps hipcc from re-packing the scalar f32 arithmetic of the bf16-pipe kernel into
              # v_pk_* instructions, which are slow beside MFMAs (mlp_bwd.hip, gelu_and_grad1)
              (os.path.join(OBJ_DIR, "mlp_bwd.o"), os.path.join(CSRC, "mlp_bwd.hip"), ["-fno-slp-vectorize"]),
+             # the bf16 producer backward: a unit of its own (mlp_bwd's and mlp_fwd_bf16's ISA is what it was); the flag for
+             # the same reason as mlp_bwd's. NO_SCRATCH_UNITS: its kernels must not spill
+             (os.path.join(OBJ_DIR, "mlp_bwd_bf16.o"), os.path.join(CSRC, "mlp_bwd_bf16.hip"), ["-fno-slp-vectorize"]),
              (os.path.join(OBJ_DIR, "mlp_wide.o"), os.path.join(CSRC, "mlp_wide.hip"), ["-fno-slp-vectorize"])]
     for t in WIN_TGS:
         units.append((os.path.join(OBJ_DIR, f"fwd_window_tgs{t}.o"), os.path.join(CSRC, "fwd_window_inst.hip"),
@@ -127,15 +130,44 @@ def _unit_table():
     return [(o, s, e, True) for o, s, e in units]
 
 
+def check_no_scratch(unit_name: str, asm_path: str) -> dict:
+    """The resources of a unit's kernels; raises when one of them uses scratch memory, or when the metadata names no kernel (a
+    layout of the metadata this reader does not know must not pass for "no scratch")."""
+    res = kernel_resources(asm_path)
+    spilled = {k: v["private_segment"] for k, v in res.items() if v.get("private_segment", 0)}
+    if spilled or not res:
+        raise RuntimeError(f"{unit_name}: kernels use scratch memory (or none found): {spilled} (kept: {asm_path})")
+    return res
+
+
 # the kernels the round-4 wrong result was seen in (and their single-launch sibling): failing-form R3 sites are errors here
 R3_STRICT_UNITS = ("fwd_mlp_step", "mixer_lds")
 LINT_LOG = os.path.join(OBJ_DIR, "isa_lint.log")  # one line per unit: functions, errors, notes, R3-pattern sites
+# units none of whose kernels may use scratch memory (a spill): checked in the code-object metadata of the kept assembly
+NO_SCRATCH_UNITS = ("mlp_bwd_bf16",)
+
+
+def kernel_resources(asm_path: str) -> dict:
+    """{kernel symbol: {"private_segment": bytes, "vgpr": n, "agpr": n, "lds": bytes}} from the code-object metadata at the end
+    of a gfx950 assembly file (a kernel's entry is a list item at two spaces, its scalar keys at four)."""
+    import re
+    keys = {".private_segment_fixed_size": "private_segment", ".vgpr_count": "vgpr", ".agpr_count": "agpr",
+            ".group_segment_fixed_size": "lds", ".name": "name"}
+    entries = []
+    with open(asm_path) as fh:
+        for line in fh:
+            m = re.match(r"^(  - | {4})(\.\w+):\s*(\S+)\s*$", line)
+            if m and m.group(1) == "  - ":
+                entries.append({})
+            if m and entries and m.group(2) in keys:
+                entries[-1][keys[m.group(2)]] = m.group(3)
+    return {e["name"]: {k: int(v) for k, v in e.items() if k != "name"} for e in entries if "name" in e and "vgpr" in e}
 
 
 def _unit_weight(unit) -> int:
     """Rough compile cost of a unit (seconds on this container), for the order in which the pool starts them."""
     name = os.path.basename(unit[0])
-    for prefix, w in (("fwd_mlp_step", 30), ("mlp_bwd", 28), ("fwd_chain_lds", 26), ("mlp_wide", 24), ("fwd_window", 16),
+    for prefix, w in (("fwd_mlp_step", 30), ("mlp_bwd_bf16", 12), ("mlp_bwd", 28), ("fwd_chain_lds", 26), ("mlp_wide", 24), ("fwd_window", 16),
                       ("bwd_window_mid", 14), ("bwd_window", 12), ("bwd_fused_bf16", 10), ("mixer_lds", 10), ("mlp_fwd", 8), ("psf_chord", 8)):
         if name.startswith(prefix):
             return w
@@ -193,6 +225,11 @@ def _compile(unit, cc, verbose):
                 fh.write(report)
         if verbose:
             print(report, end="", file=sys.stderr)
+        if unit_name.startswith(NO_SCRATCH_UNITS):
+            res = check_no_scratch(unit_name, asm[0])
+            with _LOG_LOCK:
+                with open(LINT_LOG, "a") as fh:
+                    fh.write("".join(f"  resources {unit_name} {k}: {v}\n" for k, v in sorted(res.items())))
         if errs:
             raise RuntimeError(f"isa_lint rejects {os.path.basename(real_obj)} (kept: {asm[0]}):\n" + "\n".join(errs[:20]))
         os.replace(obj, real_obj)

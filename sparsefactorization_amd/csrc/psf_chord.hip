@@ -1144,7 +1144,8 @@ const char* psf_build_info(void) {
          " | mixer: W_m computed inside the chain step (per-step kernels; one LDS-resident launch for short sequences)"
          " | bf16 chord path: f32 accumulation, one rounding per element; fwd: generic + LDS-window<bf16, TG<=16, NT=256, R=2>; bwd: fused dV+dW step<bf16, TG<=16, NT=256> (aligned full tiles), LDS-window dV<R=2> / dW<R=1><bf16, TG<=16> + generic;"
          " backward chain issued by the library (per-step launches)"
-         " | bf16 producers: fused MLP fwd<bf16> (one MFMA term, hidden layer in registers, E <= 64, inference)"
+         " | bf16 producers: fused MLP fwd<bf16> (one MFMA term, hidden layer in registers, E <= 64) + fused MLP bwd<bf16> (one MFMA"
+         " term on dual-use LDS planes, the roundings of bf16 autograd, E <= 32; training route opt-in)"
          " | bf16 mixer: one LDS-resident launch for short sequences (N <= 512, C = 8 or 16), the bits of the two-call route"
          " | arithmetic of the chord path: uncontracted mul+add (bf16: exact products fused), links ascending"
 #ifdef PSF_CSRC_HASH

@@ -22,6 +22,7 @@ enabled = True        # module-level switches (tests / A-B timing), read at ever
 train_enabled = True
 wide_enabled = True
 bf16_enabled = True
+bf16_train_route = "never"  # "always": a bf16 call that needs a gradient takes "bf16_train" (below) instead of "stacked"
 
 #: name: (predicate, function), in the order ``route`` asks the predicates; ``apply`` calls ``function(x, blocks)`` of the first
 #: that says yes. Names, not functions: both are looked up in this module when a call is routed, so a test or an A-B script
@@ -44,8 +45,15 @@ ROUTES = {
     # MFMA term per product, the three roundings of the layer-by-layer evaluation. It shares no call with the three above
     # (they want f32) and comes before the stacked route, which takes every dtype, at every T: 3.3-5.7 x faster than
     # stacked_apply at every size of profiles/bf16_mlp_ab.md (1 024 tokens: 398.9 -> 109.8 us per call; 1 048 576 tokens:
-    # 1947.7 -> 342.9 us). Training in bf16, autocast with f32 parameters and the LRA widths in bf16 go on to ``stacked_apply``.
+    # 1947.7 -> 342.9 us). Training in bf16 (unless "bf16_train" below is switched on), autocast with f32 parameters and the LRA
+    # widths in bf16 go on to ``stacked_apply``.
     "bf16_forward": ("bf16_eligible", "fused_mlp_forward_bf16"),
+    # ... under autograd, opt-in (``bf16_train_route = "always"``; the default "never" leaves training on ``stacked_apply``).
+    # psf_mlp_fwd_bf16 forward, saving only ``data`` and the parameters, and psf_mlp_bwd_bf16 (csrc/mlp_bwd_bf16.hip) backward:
+    # the hidden layer recomputed with the forward's bits, the roundings of PyTorch's bf16 autograd on the stacked route (one per
+    # tensor it materialises), dX accumulated over all MLPs in f32 and rounded once, weight gradients reduced in a fixed order.
+    # The two [T, sum h] bf16 activations of the stacked route are neither written nor read back. E <= 32, at most MAX_K MLPs.
+    "bf16_train": ("bf16_trainable", "fused_mlp_apply_bf16"),
     # Last, whatever no kernel of ours took (fp64, odd widths), on library GEMMs laid out for it: the M+1 first layers share
     # their input, so they run as ONE Linear(E, sum h) — one GEMM forward, one for the input gradient (K = sum h, instead of
     # M+1 GEMMs plus M accumulations of a [T, E] tensor) and one for the weight gradient; GELU and its backward one kernel each.
@@ -61,6 +69,7 @@ MAX_K = 32            # MLPs per launch of the narrow kernels
 _NARROW = _Limits(torch.float32, 4, 64, 4, 128, 32, 1 << 30, False)
 _NARROW_TRAIN = _NARROW._replace(e_max=32, k_max=MAX_K)
 _BF16 = _Limits(torch.bfloat16, 8, 64, 8, 128, 32, 1 << 30, True)
+_BF16_TRAIN = _BF16._replace(e_max=32, k_max=MAX_K)
 _WIDE = _Limits(torch.float32, 16, 1024, 16, 128, 128, 24, False)
 _ANY = _Limits(None, 0, 1 << 30, 1, 1 << 30, 1 << 30, 1 << 30, False)
 
@@ -132,6 +141,12 @@ def bf16_eligible(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
     return enabled and bf16_enabled and not _needs_grad(x, blocks) and _walk(x, blocks, _BF16) is not None
 
 
+def bf16_trainable(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
+    """Training in bf16, opt-in: ``fused_mlp_apply_bf16`` (psf_mlp_fwd_bf16 + psf_mlp_bwd_bf16) can replace the stacked route."""
+    return (bf16_train_route == "always" and enabled and bf16_enabled and train_enabled and _needs_grad(x, blocks)
+            and _walk(x, blocks, _BF16_TRAIN) is not None)
+
+
 def wide_ok(x: torch.Tensor, blocks: Sequence[nn.Module]) -> bool:
     """The wide kernels (psf_mlp_wide_*) can replace ``[b(x) for b in blocks]``, with or without autograd."""
     pairs = _walk(x, blocks, _WIDE) if enabled and wide_enabled else None
@@ -173,6 +188,12 @@ def _scratch(nbytes: int, dev) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)  # the caching allocator aligns to 512 bytes
 
 
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """``t`` itself, or a copy when its first byte is not on a 16-byte boundary (a contiguous view into a larger buffer — the
+    gradients of the W_m are such views of one [M, B, N, L] tensor — keeps its storage offset through ``contiguous()``)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def _bytes(kernel: str, entry: str, *args) -> int:
     """What the library's ``entry(*args)`` asks for ``kernel``; sizes outside the kernel's limits raise."""
     nbytes = getattr(_lib.load(), entry)(*args)
@@ -208,13 +229,14 @@ def _backward_raw(x2: torch.Tensor, params: Sequence[torch.Tensor], gys: Sequenc
     K, h, O = _sizes(params)
     grads = [torch.empty_like(p) for p in params]
     dX = torch.empty_like(x2) if need_dx else None
-    ws = _scratch(_bytes("psf_mlp_bwd", "psf_mlp_bwd_workspace", T, E, K, h, O), dev)  # packed weights + per-wave partial sums
+    kernel, entry = ("psf_mlp_bwd_bf16",) * 2 if x2.dtype == torch.bfloat16 else ("psf_mlp_bwd", "psf_mlp_bwd_f32")
+    ws = _scratch(_bytes(kernel, kernel + "_workspace", T, E, K, h, O), dev)  # packed weights + per-workgroup partial sums
     with torch.cuda.device(dev):
-        rc = _lib.load().psf_mlp_bwd_f32(x2.data_ptr(), T, E, K, _ptrs(params[0::4]), _ptrs(params[1::4]), _ptrs(params[2::4]),
+        rc = getattr(_lib.load(), entry)(x2.data_ptr(), T, E, K, _ptrs(params[0::4]), _ptrs(params[1::4]), _ptrs(params[2::4]),
                                          h, O, _ptrs(gys), dX.data_ptr() if need_dx else None, _ptrs(grads[0::4]),
                                          _ptrs(grads[1::4]), _ptrs(grads[2::4]), _ptrs(grads[3::4]), ws.data_ptr(), ws.numel(),
-                                         _lib.stream_ptr(dev))
-    _lib.check(rc, "psf_mlp_bwd_f32")
+                                         _lib.stream_ptr(dev))  # psf_mlp_bwd_f32 and psf_mlp_bwd_bf16 take the same arguments
+    _lib.check(rc, entry)
     return dX, grads
 
 
@@ -224,6 +246,8 @@ class _FusedMLPFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, *params):
         params = tuple(p if p.is_contiguous() else p.contiguous() for p in params)  # (no graph is recorded in here: no detach)
+        if x2.dtype == torch.bfloat16:  # psf_mlp_fwd_bf16 / psf_mlp_bwd_bf16 read X as 16-byte vectors
+            x2 = _aligned16(x2)
         ctx.save_for_backward(x2, *params)
         return tuple(_forward_raw(x2, params))
 
@@ -231,15 +255,19 @@ class _FusedMLPFn(torch.autograd.Function):
     def backward(ctx, *gys):
         x2, *params = ctx.saved_tensors
         Bs = params[2::4]
-        gys = [torch.zeros((x2.shape[0], B.shape[0]), dtype=torch.float32, device=x2.device) if g is None else g.contiguous()
+        gys = [torch.zeros((x2.shape[0], B.shape[0]), dtype=x2.dtype, device=x2.device) if g is None else g.contiguous()
                for g, B in zip(gys, Bs)]
+        if x2.dtype == torch.bfloat16:  # psf_mlp_bwd_bf16 reads a tile of dY[k] as 16-byte vectors from dY[k]'s first byte
+            gys = [_aligned16(g) for g in gys]
         need_dx = ctx.needs_input_grad[0]
         # The backward kernel sizes its dY prefetch and its weight buffering for the WIDEST output of a call: one MLP
         # with more than 16 outputs (g of the LRA networks: 32 channels) would put all ~50 units of the 12 link MLPs
         # on the slower configuration. Wide and narrow MLPs therefore go in two launches and their dX are added.
+        # psf_mlp_bwd_bf16 does not size itself by the widest output (its dY planes always hold 32 columns), and its contract
+        # rounds dX ONCE over all MLPs: a bf16 call is never split.
         narrow = [k for k, B in enumerate(Bs) if B.shape[0] <= 16]
         wide = [k for k, B in enumerate(Bs) if B.shape[0] > 16]
-        if not narrow or not wide:
+        if not narrow or not wide or x2.dtype == torch.bfloat16:
             dX, grads = _backward_raw(x2, params, gys, need_dx)
             return (dX, *grads)
         grads: List[Optional[torch.Tensor]] = [None] * len(params)
@@ -278,6 +306,7 @@ def fused_mlp_apply(x: torch.Tensor, blocks: Sequence[nn.Module]) -> List[torch.
     return [y.reshape(*lead, y.shape[1]) for y in ys]
 
 
+fused_mlp_apply_bf16 = fused_mlp_apply      # of a bf16 model: psf_mlp_fwd_bf16 / psf_mlp_bwd_bf16. Caller checks ``bf16_trainable``.
 fused_mlp_forward_bf16 = fused_mlp_forward  # of a bf16 model: the fused bf16 kernel. Caller checks ``bf16_eligible`` first.
 
 
