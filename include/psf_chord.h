@@ -291,6 +291,11 @@ int psf_sum_tensors_bf16(const uint16_t* const* srcs, int32_t count, int64_t n, 
  *   aligned (16-byte alignment and counts that are multiples of 4 take the vector path). `step` = t >= 1 from the host,
  *   or, when `step_dev` is non-NULL, t is read from that device float (a captured step must see it advance). 4096
  *   elements per workgroup: the two 524 288-element tensors of a PSFNet at N = 16384 spread over 256 workgroups.
+ *   One launch takes up to 40 tensors, so a longer list is several launches. The call is validated in full before the
+ *   first launch: on an error nothing is updated. PSF_E_SHAPE: count < 0, or step_dev NULL and not step >= 1 (NaN
+ *   included), or more than 2^31 - 1 workgroups in one launch; PSF_E_NULL: a NULL table, a NULL tensor pointer or a negative
+ *   element count at any index; PSF_E_ALIGN: a tensor pointer that is not 4-byte aligned. count = 0 returns PSF_OK before
+ *   anything else is looked at; tensors of 0 elements are skipped.
  */
 int psf_adam_step_f32(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                       const int64_t* numels, int32_t count, float lr, float beta1, float beta2, float eps, float step,

@@ -79,6 +79,10 @@ __global__ void __launch_bounds__(256) adam_k(const AdamArgs a) {
   }
 }
 
+inline uintptr_t pointer_bits(const void* p, const void* g, const void* m, const void* v) {
+  return reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
+}
+
 }  // namespace
 
 extern "C" int psf_adam_step_f32(float* const* params, const float* const* grads, float* const* exp_avg,
@@ -88,6 +92,19 @@ extern "C" int psf_adam_step_f32(float* const* params, const float* const* grads
   if (count == 0) return PSF_OK;
   if (!params || !grads || !exp_avg || !exp_avg_sq || !numels) return psf_internal_fail(PSF_E_NULL, "psf_adam_step: NULL table");
   if (!step_dev && !(step >= 1.0f)) return psf_internal_fail(PSF_E_SHAPE, "psf_adam_step: step must be >= 1");
+  // validated in full before the first launch: on an error nothing is updated
+  for (int base = 0; base < count; base += kAdamMax) {
+    const int take = count - base < kAdamMax ? count - base : kAdamMax;
+    int64_t blocks = 0;
+    for (int k = base; k < base + take; ++k) {
+      if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || numels[k] < 0)
+        return psf_internal_fail(PSF_E_NULL, "psf_adam_step: NULL tensor pointer or negative size");
+      if (pointer_bits(params[k], grads[k], exp_avg[k], exp_avg_sq[k]) & 3)
+        return psf_internal_fail(PSF_E_ALIGN, "psf_adam_step: pointers must be 4-byte aligned");
+      blocks += (numels[k] + kAdamChunk - 1) / kAdamChunk;
+      if (blocks > 0x7fffffff) return psf_internal_fail(PSF_E_SHAPE, "psf_adam_step: too many elements");
+    }
+  }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   for (int base = 0; base < count; base += kAdamMax) {
     const int take = count - base < kAdamMax ? count - base : kAdamMax;
@@ -98,16 +115,11 @@ extern "C" int psf_adam_step_f32(float* const* params, const float* const* grads
     }
     for (int i = 0; i < take; ++i) {
       const int k = base + i;
-      if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || numels[k] < 0)
-        return psf_internal_fail(PSF_E_NULL, "psf_adam_step: NULL tensor pointer or negative size");
       a.p[i] = params[k]; a.g[i] = grads[k]; a.m[i] = exp_avg[k]; a.v[i] = exp_avg_sq[k]; a.n[i] = numels[k];
-      const uintptr_t bits = reinterpret_cast<uintptr_t>(params[k]) | reinterpret_cast<uintptr_t>(grads[k]) |
-                             reinterpret_cast<uintptr_t>(exp_avg[k]) | reinterpret_cast<uintptr_t>(exp_avg_sq[k]);
-      if (bits & 3) return psf_internal_fail(PSF_E_ALIGN, "psf_adam_step: pointers must be 4-byte aligned");
+      const uintptr_t bits = pointer_bits(params[k], grads[k], exp_avg[k], exp_avg_sq[k]);
       a.vec4[i] = ((bits & 15) == 0 && (numels[k] & 3) == 0) ? 1 : 0;
       a.start[i] = (int32_t)blocks;
       blocks += (numels[k] + kAdamChunk - 1) / kAdamChunk;
-      if (blocks > 0x7fffffff) return psf_internal_fail(PSF_E_SHAPE, "psf_adam_step: too many elements");
     }
     for (int i = take; i <= kAdamMax; ++i) a.start[i] = (int32_t)blocks;
     a.count = take;

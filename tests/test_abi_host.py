@@ -286,6 +286,44 @@ def test_producer_entry_points_validate_before_touching_the_gpu(lib):
     assert b"strides" in lib.psf_last_error()
 
 
+def test_adam_step_is_validated_in_full_before_the_first_launch(lib):
+    """psf_adam_step_f32 puts 40 tensors into a launch. A fault behind the first 40 (or 80) tensors of a list comes back as its
+    code before anything is launched: these pointers are fake, so wherever there is a device a launch on the tensors in front
+    of the fault would be an illegal access (tests/test_gpu_adam.py shows on real tensors that none of them has changed)."""
+    vp, i64 = ctypes.c_void_p, ctypes.c_int64
+    f = lib.psf_adam_step_f32
+    hyper = (1e-3, 0.9, 0.999, 1e-8)
+
+    def tables(count, fault=None, at=None):
+        tabs = [[4096 + 64 * (4 * k + j) for k in range(count)] for j in range(4)]
+        sizes = [16] * count
+        if fault == "null":
+            tabs[2][at] = None
+        elif fault == "align":
+            tabs[1][at] += 2
+        elif fault == "negative":
+            sizes[at] = -1
+        elif fault == "blocks":  # 2^31 - 1 workgroups of 4096 elements, and one more, inside one launch
+            sizes[at - 1], sizes[at] = 4096 * (2 ** 31 - 1), 1
+        return [(vp * max(count, 1))(*t) for t in tabs] + [(i64 * max(count, 1))(*sizes)]
+
+    for fault, code in (("null", -1), ("negative", -1), ("align", -4), ("blocks", -2)):
+        for at in (40, 79, 80):
+            if fault == "blocks" and at in (40, 80):
+                continue  # (the count is per launch: index at - 1 would sit in the launch before)
+            assert f(*tables(81, fault, at), 81, *hyper, 1.0, None, None) == code, (fault, at)
+            assert b"psf_adam_step" in lib.psf_last_error()
+    t81 = tables(81)
+    for step in (0.5, 0.0, -1.0, float("nan")):
+        assert f(*t81, 81, *hyper, step, None, None) == -2 and b"step" in lib.psf_last_error()   # PSF_E_SHAPE
+    assert f(*t81, -1, *hyper, 1.0, None, None) == -2                                             # count < 0
+    assert f(*t81, 0, *hyper, 1.0, None, None) == 0 and f(None, None, None, None, None, 0, *hyper, 0.5, None, None) == 0
+    for j in range(5):                                                                            # a NULL table
+        t = list(t81)
+        t[j] = None
+        assert f(*t, 81, *hyper, 1.0, None, None) == -1
+
+
 # The keys of the library: the parent's nineteen chord knobs (its twenty-one less the two timing-lab keys, which left with the
 # labs) and the two that the producer entry points read.
 KNOB_KEYS = ["fwd_variant", "bwd_variant", "xcd_remap", "fwd_split", "fwd_wide", "dw_variant", "dv_threads", "bwd_fused",
