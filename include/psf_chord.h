@@ -547,7 +547,8 @@ int psf_mlp_bwd_bf16(const uint16_t* X, int64_t T, int32_t E, int32_t K, const u
  *                         NULL and a workspace of psf_mlp_wide_fwd_workspace + psf_mlp_wide_saved_bytes bytes.
  *   psf_mlp_wide_bwd_f32  the gradients of psf_mlp_bwd_f32 from `saved` and dY[k]; dX may be NULL (not computed).
  *   Layouts as psf_mlp_fwd_f32 / psf_mlp_bwd_f32. Limits: E a multiple of 16, 16 <= E <= 1024; 1 <= h[k] <= 128;
- *   1 <= O[k] <= 128; 1 <= K <= 24; T * E and T * (sum of h[k] rounded up to 32) below 2^30; X and A[k] 16-byte aligned.
+ *   1 <= O[k] <= 128; 1 <= K <= 24; T_pad * E and T_pad * (sum of h[k], each rounded up to 32) below 2^30, T_pad being T
+ *   rounded up to 256; X and the forward's A[k] 16-byte aligned, every other array 4-byte aligned (any float pointer).
  *   Workspaces: caller-owned, 256-byte aligned, at least psf_mlp_wide_{fwd,bwd}_workspace bytes (-1: unsupported sizes).
  * Every reduction has a fixed order (no float atomics): results are bit-reproducible run to run.
  */

@@ -741,7 +741,10 @@ bool make_wide_plan(int64_t T, int32_t E, int32_t K, const int32_t* h, const int
   if (s > chunks / 32) s = (int)(chunks / 32);
   if (s > kSplitsMax) s = kSplitsMax;
   if (s < 1) s = 1;
-  p->splits = s;
+  // x3_gemm_k cuts per = ceil(chunks / splits) chunks per split: with s splits the last ones can be left without any
+  // (chunks = 1584, s = 49: per = 33, and 48 x 33 = 1584). Keep only the splits that get a K range; per stays what it was.
+  const int64_t per = (chunks + s - 1) / s;
+  p->splits = (int32_t)((chunks + per - 1) / per);
   return true;
 }
 
@@ -755,7 +758,10 @@ int64_t bwd_ws_bytes(const WidePlan& p) {
 }
 
 hipError_t launch_gemm(bool tn, bool narrow, const GemmArgs& ga, hipStream_t s) {
-  if (ga.splits < 1 || ga.chunks < ga.splits) return hipErrorInvalidValue;  // every (tile, split) item needs a K range
+  // every (tile, split) item needs a K range: the kernel gives split sp the chunks [sp * per, min((sp + 1) * per, chunks))
+  if (ga.splits < 1 || ga.chunks < ga.splits) return hipErrorInvalidValue;
+  const int64_t per = ((int64_t)ga.chunks + ga.splits - 1) / ga.splits;
+  if ((int64_t)(ga.splits - 1) * per >= ga.chunks) return hipErrorInvalidValue;
   const int64_t items = (int64_t)ga.tiles_m * ga.tiles_n * ga.splits;
   const dim3 grid((unsigned)(items < 256 ? items : 256));  // persistent: one workgroup per CU of the MI355X
   if (tn && narrow) hipLaunchKernelGGL((x3_gemm_k<true, GemmNarrow>), grid, dim3(kGemmThreads), 0, s, ga);

@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(kGemmThreads, 1) x3_gemm_k(const GemmArgs g) {
   }
   const uint32_t per_split = (uint32_t)(g.tiles_m * g.tiles_n);
   const uint32_t items = per_split * (uint32_t)g.splits;
-  const int per = (g.chunks + g.splits - 1) / g.splits;  // host guarantees every split a non-empty K range
+  const int per = (g.chunks + g.splits - 1) / g.splits;  // launch_gemm refuses a plan that leaves a split without a K range
   struct Item {
     int64_t m0, n0;
     int sp, k_begin, nk;

@@ -286,6 +286,90 @@ def test_producer_entry_points_validate_before_touching_the_gpu(lib):
     assert b"strides" in lib.psf_last_error()
 
 
+def test_wide_producer_entry_points_validate_before_touching_the_gpu(lib):
+    """psf_mlp_wide_fwd_f32 / psf_mlp_wide_bwd_f32 (csrc/mlp_wide.hip) refuse, in this order and before any HIP call: a NULL
+    table (-1), a shape outside the limits (-2), X off 16 bytes or saved / workspace off 256 (-4), a saved or workspace area
+    one byte short (-2), a NULL pointer of any kind in a table (-1), and — forward only — A[k] off 16 bytes (-4). Every pointer
+    here is fake: a call that got past its checks would launch on them."""
+    i32, vp = ctypes.c_int32, ctypes.c_void_p
+    K, T, E = 2, 100, 32
+
+    def arr(vals):
+        return (i32 * len(vals))(*vals)
+
+    def tab(hole=None, v=64):
+        return (vp * K)(*[None if k == hole else v for k in range(K)])
+
+    h, O = arr([32, 128]), arr([8, 40])
+    n_saved, n_fwd, n_bwd = (f(T, E, K, h, O) for f in (lib.psf_mlp_wide_saved_bytes, lib.psf_mlp_wide_fwd_workspace,
+                                                        lib.psf_mlp_wide_bwd_workspace))
+    assert min(n_saved, n_fwd, n_bwd) > 0
+    X, SAVED, WS = vp(16), vp(1 << 20), vp(1 << 24)   # 16-byte and 256-byte aligned
+
+    # ---- forward: (X, T, E, K, A, a, B, b, h, O, Y, saved, saved_bytes, workspace, workspace_bytes, stream)
+    f = lib.psf_mlp_wide_fwd_f32
+
+    def fwd(**kw):
+        a = dict(X=X, T=T, E=E, K=K, A=tab(), a=tab(), B=tab(), b=tab(), h=h, O=O, Y=tab(), saved=SAVED, n_saved=n_saved, ws=WS, n_ws=n_fwd)
+        a.update(kw)
+        rc = f(a["X"], a["T"], a["E"], a["K"], a["A"], a["a"], a["B"], a["b"], a["h"], a["O"], a["Y"], a["saved"], a["n_saved"],
+               a["ws"], a["n_ws"], None)
+        assert rc != 0 and b"psf_mlp_wide_fwd" in lib.psf_last_error(), kw
+        return rc
+
+    for name in ("X", "A", "a", "B", "b", "h", "O", "Y", "ws"):                      # 1. a NULL table, before the shape ...
+        assert fwd(**{name: None}) == -1, name
+        assert fwd(**{name: None}, T=0) == -1, name
+    for kw in (dict(T=0), dict(E=8), dict(E=1040), dict(E=520), dict(K=0), dict(K=25), dict(h=arr([0, 128])), dict(h=arr([32, 129])),
+               dict(O=arr([0, 40])), dict(O=arr([8, 129]))):                          # 2. ... the shape before the alignment ...
+        assert fwd(**kw) == -2, kw
+        assert fwd(**kw, X=vp(20), n_ws=0) == -2, kw
+    for kw in (dict(X=vp(20)), dict(X=vp(24)), dict(saved=vp((1 << 20) + 16)), dict(ws=vp((1 << 24) + 128))):
+        assert fwd(**kw) == -4, kw                                                    # 3. ... the alignment before the sizes ...
+        assert fwd(**kw, n_ws=0, n_saved=0) == -4, kw
+    for kw in (dict(n_saved=n_saved - 1), dict(n_ws=n_fwd - 1), dict(saved=None, n_saved=0, n_ws=n_fwd),
+               dict(saved=None, n_saved=0, n_ws=n_fwd + n_saved - 1)):
+        assert fwd(**kw) == -2 and b"too small" in lib.psf_last_error(), kw          # 4. ... the sizes before the layers
+        assert fwd(**kw, A=tab(hole=0)) == -2, kw
+    for name in ("A", "a", "B", "b", "Y"):                                            # 5. a NULL pointer of every kind, any layer
+        for k in range(K):
+            assert fwd(**{name: tab(hole=k)}) == -1 and b"NULL layer pointer" in lib.psf_last_error(), (name, k)
+    for k in range(K):                                                                # 6. the forward's A[k] off 16 bytes
+        bad = (vp * K)(*[68 if j == k else 64 for j in range(K)])
+        assert fwd(A=bad) == -4 and b"first-layer weights" in lib.psf_last_error(), k
+        for name in ("a", "B", "b", "Y"):                                             # (nothing else needs more than a float's)
+            assert fwd(A=bad, **{name: tab(v=68)}) == -4 and fwd(A=tab(hole=k), **{name: tab(v=68)}) == -1
+
+    # ---- backward: (saved, saved_bytes, T, E, K, A, B, h, O, dY, dX, dA, da, dB, db, workspace, workspace_bytes, stream)
+    g = lib.psf_mlp_wide_bwd_f32
+
+    def bwd(**kw):
+        a = dict(saved=SAVED, n_saved=n_saved, T=T, E=E, K=K, A=tab(), B=tab(), h=h, O=O, dY=tab(), dX=vp(32), dA=tab(), da=tab(),
+                 dB=tab(), db=tab(), ws=WS, n_ws=n_bwd)
+        a.update(kw)
+        rc = g(a["saved"], a["n_saved"], a["T"], a["E"], a["K"], a["A"], a["B"], a["h"], a["O"], a["dY"], a["dX"], a["dA"], a["da"],
+               a["dB"], a["db"], a["ws"], a["n_ws"], None)
+        assert rc != 0 and b"psf_mlp_wide_bwd" in lib.psf_last_error(), kw
+        return rc
+
+    for name in ("saved", "A", "B", "h", "O", "dY", "dA", "da", "dB", "db", "ws"):
+        assert bwd(**{name: None}) == -1, name
+        assert bwd(**{name: None}, T=0) == -1, name
+    for kw in (dict(T=0), dict(E=520), dict(K=25), dict(h=arr([32, 129])), dict(O=arr([0, 40]))):
+        assert bwd(**kw) == -2, kw
+        assert bwd(**kw, saved=vp((1 << 20) + 16)) == -2, kw
+    for kw in (dict(saved=vp((1 << 20) + 16)), dict(ws=vp((1 << 24) + 128))):
+        assert bwd(**kw) == -4, kw
+        assert bwd(**kw, n_ws=0, n_saved=0) == -4, kw
+    for kw in (dict(n_saved=n_saved - 1), dict(n_ws=n_bwd - 1)):
+        assert bwd(**kw) == -2 and b"too small" in lib.psf_last_error(), kw
+        assert bwd(**kw, dY=tab(hole=1)) == -2, kw
+    for name in ("A", "B", "dY", "dA", "da", "dB", "db"):
+        for k in range(K):
+            assert bwd(**{name: tab(hole=k)}) == -1 and b"NULL layer pointer" in lib.psf_last_error(), (name, k)
+            assert bwd(**{name: tab(hole=k)}, dX=None) == -1, (name, k)
+
+
 def test_adam_step_is_validated_in_full_before_the_first_launch(lib):
     """psf_adam_step_f32 puts 40 tensors into a launch. A fault behind the first 40 (or 80) tensors of a list comes back as its
     code before anything is launched: these pointers are fake, so wherever there is a device a launch on the tensors in front
