@@ -178,6 +178,15 @@ int psf_chord_spmm_fwd_bf16(const uint16_t* W, const uint16_t* V, const uint16_t
  *   W  [B,N,L]  needed for dV;   V [B,N,C] or [N,C] (v_batch_stride == 0) needed for dW
  *   dW [B,N,L]
  *   dV [B,N,C]  always per batch element; when V was broadcast the caller sums dV over b
+ * What f32 dW is (dV is the oracle's bits, links ascending): each element is an f32 sum of the C products dZ[b,p,c] *
+ * V[b,(p+off_k) mod N,c], every product and every addition rounded to nearest, in an order that belongs to the kernel
+ * (channels split over lanes and chunks, combined by a tree) and so may differ between kernels, knobs "bwd_variant",
+ * "bwd_fused", "dw_variant" and "dw_tgs", and from the oracle's left-to-right sum. Therefore
+ *     |dW - exact| <= gamma_C * sum_c |dZ * V|,   gamma_C = C u / (1 - C u),  u = 2^-24,
+ * per element; dW is exact, bit for bit on every route, whenever every partial sum of the row dot is representable
+ * (integer data below 2^24, say); links that reduce to the same offset mod N give the same bits; the launch-shape knobs
+ * ("fwd_split", "bwd_fronts", "bwd_fused_wg_limit") change no bit. It is not bit-identical to the oracle.
+ * tests/test_gpu_dw_f32_exact.py holds every dW kernel to this.
  */
 int psf_chord_spmm_bwd_f32(const float* dZ, const float* W, const float* V, float* dW, float* dV,
                            int64_t B, int64_t N, int32_t L, int64_t C, int64_t v_batch_stride,

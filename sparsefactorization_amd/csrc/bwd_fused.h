@@ -11,7 +11,9 @@
 //   the two W tiles under the dZ window (flat 16-byte-chunk images),
 // loads the far-link operands into registers (dZ rows and W column elements for dV, V rows for dW), then computes dV
 // (links ascending, uncontracted:
-// bit-identical to chord_dv_win_k and the oracle), the row dots of dW (same order as chord_dw_win_k) and writes the dW
+// bit-identical to chord_dv_win_k and the oracle), the row dots of dW (a lane's four products summed pairwise, (p0 + p2) +
+// (p1 + p3), then chord_dw_win_k's lane tree: NOT the window kernel's bits — it sums the four left to right — but, like
+// it, an f32 sum of the C products, exact whenever every partial sum is: tests/test_gpu_dw_f32_exact.py) and writes the dW
 // tile flat through LDS (the image reuses the first W tile's bytes).
 // Full tiles only: N a multiple of TR, C / 4 = TG exactly, chunk-clean W / dW buffers; the host sends anything else to
 // the two-kernel path.
