@@ -137,7 +137,7 @@ def test_listops_network_takes_the_wide_path(gpu):
     from sparsefactorization_amd import fused_mlp, lra_training
     torch.manual_seed(0)
     net = lra_training.build_model("listops").to(gpu)
-    ref = copy.deepcopy(net)
+    ref = copy.deepcopy(net).double()  # (X holds token ids: unchanged)
     X, Y = lra_training.synthetic_split("listops", 2, gpu, 1)
     X = lra_training.add_cls_token(X, lra_training.config["listops"]["model"]["vocab_size"])
     calls = []
