@@ -160,11 +160,12 @@ int psf_chord_spmm_fwd_f64(const double* W, const double* V, const double* res, 
  *                 4-byte aligned for even L, and the measured gate (knobs "chain_fused", "chain_cc") takes it;
  *                 otherwise M per-step launches. psf_describe_chain_fwd_dtype names the route.
  *                 Backward chain: psf_chord_chain_bwd_bf16 issues the per-step launches and the one residual sum inside
- *                 the library (below).
+ *                 the library; psf_chord_chain_bwd_lds_bf16 is the whole chain in ONE launch for N <= 1024, C = 8 or 16,
+ *                 bit-identical to it (both below).
  *                 Producer MLPs, forward (inference): psf_mlp_fwd_bf16 (below, next to psf_mlp_fwd_f32).
  *                 Mixer of a short sequence in one launch (inference): psf_mixer_fwd_bf16 (below, next to psf_mixer_fwd_f32).
  * Not covered: float16, mixed dtypes, the bf16 mixer with W computed inside per-step kernels (long sequences) or from an
- *                 input recipe, the bf16 flat-head entry, the bf16 producer backward, a one-launch bf16 backward chain, and
+ *                 input recipe, the bf16 flat-head entry, the bf16 producer backward, and
  *                 an edge instance of the bf16 fused backward step (ragged N, other far offsets, W / dW off their 16-byte
  *                 boundary: those steps run the dW and dV window kernels).
  */
@@ -258,6 +259,31 @@ int psf_chord_chain_bwd_bf16(const uint16_t* dOut, const uint16_t* const* W_step
                              const uint16_t* const* X_steps, uint16_t* const* dW_steps, uint16_t* dV0,
                              uint16_t* const* dX_steps, int32_t M, int32_t use_residual,
                              int64_t B, int64_t N, int32_t L, int64_t C, const int64_t* offsets, void* stream);
+/*
+ * The bf16 backward chain of a short sequence in exactly ONE kernel launch (chord_chain_bwd_lds_k<bf16>,
+ * csrc/bwd_chain_lds_bf16.h): one workgroup per sequence, the running gradient, X_m and W_m in LDS, dW_m written per step,
+ * dV0 once at the end; no g_m reaches memory, so there is no dX_steps argument and no scratch gradient buffer. The entry does
+ * not allocate and does not synchronise.
+ *   Covered: 1 <= N <= 1024, C = 8 or 16, 2 <= L <= 20, 1 <= M <= 64, B <= 2^31 - 1, any offsets (NULL = the chord pattern).
+ *   psf_chord_chain_bwd_lds_bf16_supported answers 1 / 0 for a shape (0 as well under knob "chain_bwd_fused" = 0).
+ *   Arguments and validation as psf_chord_chain_bwd_bf16: X_steps[0] is ignored (V0 is used), NULL and alias checks, B == 0
+ *   returns PSF_OK. PSF_E_UNSUPPORTED — never a per-step fallback — for a shape that is not covered or under knob
+ *   "chain_bwd_fused" = 0: the caller uses psf_chord_chain_bwd_bf16 then.
+ *   Alignment: dOut, dV0 and every X_m 16 bytes (PSF_E_ALIGN otherwise); W_m and dW_m ANY 2-byte alignment — they are read
+ *   and written element by element, nothing outside [W_m, W_m + B*N*L) is read, nothing outside [dW_m, dW_m + B*N*L) or
+ *   [dV0, dV0 + B*N*C) is written.
+ *   Arithmetic: the bits of psf_chord_chain_bwd_bf16 at 16-byte-aligned operands. g_m: f32 accumulator from +0, links
+ *   ascending, one fused multiply-add per term (the bf16 product is exact in f32), rounded to bf16 once (nearest even, NaN
+ *   kept), and that rounded value enters the next step. dW_m[p,k]: per 8-channel group a running fused multiply-add over the
+ *   channels ascending from +0; C = 8 rounds that partial, C = 16 rounds the f32 sum of the two partials. Residual:
+ *   dV0 = ((g_M + g_{M-1}) + ... + g_1) + g_0 over the rounded g_m, summed left to right in f32, rounded once; without it
+ *   dV0 = g_0.
+ */
+int psf_chord_chain_bwd_lds_bf16_supported(int64_t N, int32_t L, int64_t C, int32_t M);
+int psf_chord_chain_bwd_lds_bf16(const uint16_t* dOut, const uint16_t* const* W_steps, const uint16_t* V0,
+                                 const uint16_t* const* X_steps, uint16_t* const* dW_steps, uint16_t* dV0,
+                                 int32_t M, int32_t use_residual, int64_t B, int64_t N, int32_t L, int64_t C,
+                                 const int64_t* offsets, void* stream);
 
 /*
  * (Rounds 2-4 also exported training variants that kept a link-major side copy of W's far columns for the dV kernel —

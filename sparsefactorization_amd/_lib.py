@@ -43,6 +43,10 @@ SIGNATURES = {
                                  c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
     "psf_chord_chain_bwd_bf16": ([c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_i32, c_i32,
                                   c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
+    # the bf16 backward chain in one launch (no dX_steps): PSF_E_UNSUPPORTED where it does not apply, never a fallback
+    "psf_chord_chain_bwd_lds_bf16_supported": ([c_i64, c_i32, c_i64, c_i32], ctypes.c_int),
+    "psf_chord_chain_bwd_lds_bf16": ([c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i32, c_i32,
+                                      c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
     "psf_linear_wgrad_workspace": ([c_i64, c_i32, c_i32], c_i64),
     "psf_linear_wgrad_f32": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),
     "psf_linear_wgrad_strided_f32": ([c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),

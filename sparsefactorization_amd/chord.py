@@ -27,6 +27,12 @@ from . import _lib
 # bfloat16: bf16 storage, f32 accumulation, one rounding per element (include/psf_chord.h, "bfloat16")
 _SUFFIX = {torch.float32: "_f32", torch.float64: "_f64", torch.bfloat16: "_bf16"}
 
+# "never" (default) or "always": whether _ChordChain.backward runs a bf16 chain that psf_chord_chain_bwd_lds_bf16 covers
+# (N <= 1024, C = 8 or 16, 2 <= L <= 20, M <= 64) in that entry's one launch, without the [M,B,N,C] gradient buffers, instead
+# of the per-step launches of psf_chord_chain_bwd_bf16. Same bits either way (csrc/bwd_chain_lds_bf16.h); opt-in like
+# fused_mlp.bf16_train_route, because the default route's launch tables are pinned (profiles/bf16_chain_bwd_ab.md)
+bf16_chain_bwd_route = "never"
+
 
 def _suffix(t: torch.Tensor) -> str:
     try:
@@ -317,25 +323,35 @@ class _ChordChain(torch.autograd.Function):
         # and the one-pass residual sum issued by the library otherwise — same kernels, same order and same bits as the loop
         # below, without M trips through ctypes and 2 M allocations (the small LRA models are bound by the host)
         # bf16 (psf_chord_chain_bwd_bf16): no one-launch kernel — always the per-step launches and the one residual sum, issued by
-        # the library; PSF_E_UNSUPPORTED where psf_sum_tensors_bf16's limits do not hold, and the loop below runs instead
+        # the library; PSF_E_UNSUPPORTED where psf_sum_tensors_bf16's limits do not hold, and the loop below runs instead.
+        # With bf16_chain_bwd_route = "always", psf_chord_chain_bwd_lds_bf16 (one launch, N <= 1024, C = 8 or 16) is tried first
         is_bf16 = g.dtype == torch.bfloat16
         if ((g.dtype == torch.float32 or is_bf16) and stride0 == N * C and all(need_w) and M >= 1
                 and not any(t.data_ptr() % 16 for t in (g, V0, *steps))):  # (views at odd offsets: the loop's kernels take them)
             one_launch = not is_bf16 and bool(lib.psf_chord_chain_bwd_supported(N, L, C, M))
+            # bf16, opt-in (bf16_chain_bwd_route): the whole chain in one launch where csrc/bwd_chain_lds_bf16.h covers the shape
+            lds_bf16 = (is_bf16 and bf16_chain_bwd_route == "always"
+                        and bool(lib.psf_chord_chain_bwd_lds_bf16_supported(N, L, C, M)))
             dWb = torch.empty((M, B, N, L), dtype=g.dtype, device=dev)
             dWs = list(dWb.unbind(0))
             dV0 = torch.empty((B, N, C), dtype=g.dtype, device=dev)
             w_tab = (ctypes.c_void_p * M)(*[w.data_ptr() for w in Ws])
             x_tab = (ctypes.c_void_p * M)(V0.data_ptr(), *[s.data_ptr() for s in steps])
             dw_tab = (ctypes.c_void_p * M)(*[d.data_ptr() for d in dWs])
-            dx_tab = None
-            if not one_launch:
-                dXb = torch.empty((M, B, N, C), dtype=g.dtype, device=dev)
-                dx_tab = (ctypes.c_void_p * M)(*[dXb[m].data_ptr() for m in range(M)])
-            with torch.cuda.device(dev):
-                chain_bwd = lib.psf_chord_chain_bwd_bf16 if is_bf16 else lib.psf_chord_chain_bwd_f32
-                rc = chain_bwd(g.data_ptr(), w_tab, V0.data_ptr(), x_tab, dw_tab, dV0.data_ptr(), dx_tab, M,
-                               1 if ctx.use_residual else 0, B, N, L, C, off, _stream_ptr(dev))
+            rc = _lib.PSF_E_UNSUPPORTED
+            if lds_bf16:  # no dXb: no g_m reaches memory. PSF_E_UNSUPPORTED (knob "chain_bwd_fused" changed since): the route below
+                with torch.cuda.device(dev):
+                    rc = lib.psf_chord_chain_bwd_lds_bf16(g.data_ptr(), w_tab, V0.data_ptr(), x_tab, dw_tab, dV0.data_ptr(), M,
+                                                          1 if ctx.use_residual else 0, B, N, L, C, off, _stream_ptr(dev))
+            if rc == _lib.PSF_E_UNSUPPORTED:
+                dx_tab = None
+                if not one_launch:
+                    dXb = torch.empty((M, B, N, C), dtype=g.dtype, device=dev)
+                    dx_tab = (ctypes.c_void_p * M)(*[dXb[m].data_ptr() for m in range(M)])
+                with torch.cuda.device(dev):
+                    chain_bwd = lib.psf_chord_chain_bwd_bf16 if is_bf16 else lib.psf_chord_chain_bwd_f32
+                    rc = chain_bwd(g.data_ptr(), w_tab, V0.data_ptr(), x_tab, dw_tab, dV0.data_ptr(), dx_tab, M,
+                                   1 if ctx.use_residual else 0, B, N, L, C, off, _stream_ptr(dev))
             if rc != _lib.PSF_E_UNSUPPORTED:
                 _lib.check(rc, "psf_chord_chain_bwd")
                 return (dV0.reshape(ctx.v_shape) if need_v0 else None, None, None, *dWs)

@@ -19,6 +19,7 @@
 #include "bwd_kernels.h"
 #include "bwd_window_launch.h"
 #include "bwd_chain_lds.h"
+#include "bwd_chain_lds_bf16.h"
 #include "fwd_chain_lds_bf16.h"
 #include "fwd_chain_lds_launch.h"
 #include "fwd_kernels.h"
@@ -833,7 +834,7 @@ int chain_impl(Tuning tn, const T* const* W_steps, const T* V0, T* const* out_st
 }
 
 // The backward chain in one library call (K = float or __bf16). f32 runs the one-launch kernel where it fits
-// (bwd_chain_lds.h; there is no one-launch bf16 backward kernel). Otherwise the M per-step launches of psf_chord_spmm_bwd_*
+// (bwd_chain_lds.h; the one-launch bf16 kernel has an entry of its own, psf_chord_chain_bwd_lds_bf16 below). Otherwise the M per-step launches of psf_chord_spmm_bwd_*
 // (the fused step where it applies), the gradient handed from dX_steps[m] to the next step, and ONE psf_sum_tensors_* pass over
 // the residual terms at the end — ((g_M + g_{M-1}) + ... + g_1) + g_0, in bf16 summed in f32 and rounded once: what the
 // caller's loop (chord.py) did, without M trips through its language's FFI.
@@ -1268,6 +1269,44 @@ int psf_chord_chain_bwd_bf16(const uint16_t* dOut, const uint16_t* const* W_step
                                 reinterpret_cast<const P*>(X_steps), reinterpret_cast<__bf16* const*>(dW_steps),
                                 reinterpret_cast<__bf16*>(dV0), reinterpret_cast<__bf16* const*>(dX_steps), M, use_residual, B, N, L,
                                 C, offsets, stream);
+}
+
+int psf_chord_chain_bwd_lds_bf16_supported(int64_t N, int32_t L, int64_t C, int32_t M) {
+  return g_chain_bwd_fused.load() && chain_bwd_lds_bf16_fits(N, C, L, M) ? 1 : 0;
+}
+
+// The bf16 backward chain in exactly one launch (bwd_chain_lds_bf16.h), or PSF_E_UNSUPPORTED: no per-step fallback here
+// (psf_chord_chain_bwd_bf16 is that route). Validation in chain_bwd_impl's order.
+int psf_chord_chain_bwd_lds_bf16(const uint16_t* dOut, const uint16_t* const* W_steps, const uint16_t* V0,
+                                 const uint16_t* const* X_steps, uint16_t* const* dW_steps, uint16_t* dV0, int32_t M,
+                                 int32_t use_residual, int64_t B, int64_t N, int32_t L, int64_t C, const int64_t* offsets,
+                                 void* stream) {
+  if (M < 1) return fail(PSF_E_SHAPE, "M must be >= 1");
+  if (!dOut || !W_steps || !V0 || !X_steps || !dW_steps || !dV0) return fail(PSF_E_NULL, "a required pointer is NULL");
+  if (int rc = check_dims(B, N, L, C, N * C)) return rc;
+  const Tuning tn = snapshot();
+  if (!tn.chain_bwd_fused || !chain_bwd_lds_bf16_fits(N, C, L, M)) return PSF_E_UNSUPPORTED;
+  if (B == 0) return PSF_OK;
+  if (B > 0x7fffffff) return fail(PSF_E_SHAPE, "B too large");
+  ChainBwdArgsBf16 a;
+  for (int m = 0; m < M; ++m) {
+    const uint16_t* x = m == 0 ? V0 : X_steps[m];
+    if (!W_steps[m] || !x || !dW_steps[m]) return fail(PSF_E_NULL, "step %d: NULL pointer", m);
+    if (dW_steps[m] == W_steps[m]) return fail(PSF_E_ALIAS, "step %d: dW aliases W", m);
+    if (!aligned_to(W_steps[m], 2) || !aligned_to(dW_steps[m], 2) || !aligned_to(x, 16))
+      return fail(PSF_E_ALIGN, "step %d: W / dW must be 2-byte, X 16-byte aligned", m);
+    a.W[m] = reinterpret_cast<const __bf16*>(W_steps[m]), a.X[m] = reinterpret_cast<const __bf16*>(x);
+    a.dW[m] = reinterpret_cast<__bf16*>(dW_steps[m]);
+  }
+  for (int m = M; m < kChainMaxSteps; ++m) a.W[m] = nullptr, a.X[m] = nullptr, a.dW[m] = nullptr;
+  if (!aligned_to(dOut, 16) || !aligned_to(dV0, 16)) return fail(PSF_E_ALIGN, "dOut and dV0 must be 16-byte aligned");
+  a.dOut = reinterpret_cast<const __bf16*>(dOut), a.dV0 = reinterpret_cast<__bf16*>(dV0);
+  a.M = M, a.N = (int32_t)N, a.C = (int32_t)C;
+  Offsets offs;
+  make_offsets(N, L, offsets, &offs);
+  hipError_t e = launch_chain_bwd_lds_bf16(L, (int)(C / 8), use_residual != 0, a, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(e, "chord_chain_bwd_lds<bf16> launch");
+  return PSF_OK;
 }
 
 int64_t psf_mixer_fwd_workspace(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {
