@@ -45,8 +45,11 @@ ROUTES = {
     # MFMA term per product, the three roundings of the layer-by-layer evaluation. It shares no call with the three above
     # (they want f32) and comes before the stacked route, which takes every dtype, at every T: 3.3-5.7 x faster than
     # stacked_apply at every size of profiles/bf16_mlp_ab.md (1 024 tokens: 398.9 -> 109.8 us per call; 1 048 576 tokens:
-    # 1947.7 -> 342.9 us). Training in bf16 (unless "bf16_train" below is switched on), autocast with f32 parameters and the LRA
-    # widths in bf16 go on to ``stacked_apply``.
+    # 1947.7 -> 342.9 us). Training in bf16 (unless "bf16_train" below is switched on) and the LRA widths in bf16 go on to
+    # ``stacked_apply``. Autocast with f32 parameters does not come here: f32 ``data`` keeps the f32 routes above, which call no
+    # autocast-eligible op and return f32 under autocast too; bf16 ``data`` (made by an autocast op upstream) with f32
+    # parameters matches NO route — every route wants x and the first layer's weight of one dtype — and ``apply`` returns None:
+    # the blocks' own layers run, which under autocast are nn.Linear (tests/test_gpu_autocast.py pins both).
     "bf16_forward": ("bf16_eligible", "fused_mlp_forward_bf16"),
     # ... under autograd, opt-in (``bf16_train_route = "always"``; the default "never" leaves training on ``stacked_apply``).
     # psf_mlp_fwd_bf16 forward, saving only ``data`` and the parameters, and psf_mlp_bwd_bf16 (csrc/mlp_bwd_bf16.hip) backward:

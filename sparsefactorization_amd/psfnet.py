@@ -32,7 +32,7 @@ from torch import nn
 
 from . import _lib, fused_mixer, fused_mlp
 from .chord import chord_chain, chord_spmm, get_chord_indices_assym
-from .token_linear import TokenEmbedding, TokenLinear, embed_tokens
+from .token_linear import TokenEmbedding, TokenLinear, autocast_on, embed_tokens
 
 LayerSpec = Sequence[Union[str, int]]
 
@@ -130,7 +130,10 @@ def _flat_head(final: nn.Module, flat: torch.Tensor) -> torch.Tensor:
             # psf_flat_head_f32 reads 16-byte vectors and returns PSF_E_ALIGN otherwise: a view at an odd storage offset (or
             # a weight view) takes the library GEMM instead of raising
             and flat.is_contiguous() and flat.data_ptr() % 16 == 0 and final.weight.is_contiguous()
-            and final.weight.data_ptr() % 16 == 0):
+            and final.weight.data_ptr() % 16 == 0
+            # J > 8 is F.linear inside the Function: under autocast its output, and so the gradient handed to the backward, is
+            # bf16 / f16. That head is then the stock module; the J <= 8 kernel calls no autocast-eligible op and stays f32
+            and (final.out_features <= 8 or not autocast_on(flat))):
         return _FlatHeadFn.apply(flat, final.weight, final.bias)
     return final(flat)
 

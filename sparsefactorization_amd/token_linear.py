@@ -19,13 +19,33 @@ MAX_WIDTH = 128   # kernel limit on in_features / out_features
 MIN_TOKENS = 4096  # below this the stock path is fine
 
 
+def autocast_on(t: torch.Tensor) -> bool:
+    """Autocast is active for ``t``'s device. An autocast-eligible op inside a custom Function (``F.linear``) then returns
+    bf16 / f16, and autograd hands the Function's backward an upstream gradient of that dtype: the kernels behind the
+    Functions here are typed by their name only, so under autocast ``TokenLinear`` and the J > 8 FLATTEN head are the stock
+    modules ("Autocast and index types"). No kernel here takes a CPU tensor; "cpu" is answered so that the
+    host tests can drive ``TokenLinear.forward`` under ``torch.autocast("cpu")``. ``TokenLinear.forward`` asks once and
+    ``wgrad_supported`` again: the second answer is for ``fused_mlp.stacked_apply``, which calls ``_TokenLinearFn`` itself."""
+    kind = t.device.type
+    return kind in ("cuda", "cpu") and torch.is_autocast_enabled(kind)
+
+
 def wgrad_supported(x2d: torch.Tensor, out_features: int) -> bool:
     return (x2d.is_cuda and x2d.dtype == torch.float32 and x2d.shape[0] >= MIN_TOKENS
-            and x2d.shape[1] <= MAX_WIDTH and out_features <= MAX_WIDTH)
+            and x2d.shape[1] <= MAX_WIDTH and out_features <= MAX_WIDTH and not autocast_on(x2d))
 
 
 def linear_wgrad(x2d: torch.Tensor, dy2d: torch.Tensor, need_bias: bool = True):
-    """(dWeight [n, m], dBias [n] or None) for X [T, m], dY [T, n] on the HIP kernel."""
+    """(dWeight [n, m], dBias [n] or None) for X [T, m], dY [T, n] on the HIP kernel. Both float32 on one HIP device:
+    anything else is a TypeError (the entry takes raw addresses and would read another dtype's bytes as floats)."""
+    operands = (("x", x2d), ("dy", dy2d))
+    for name, t in operands:  # the element type first, of both operands: the message names the one that is wrong and why
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"linear_wgrad takes float32 tensors on one HIP device; {name} is {getattr(t, 'dtype', type(t))}")
+    for name, t in operands:
+        if not t.is_cuda or t.device != x2d.device:
+            raise TypeError(f"linear_wgrad takes float32 tensors on one HIP device; {name} is on '{t.device}'"
+                            + (f", x on '{x2d.device}'" if t.is_cuda else ""))
     T, m = x2d.shape
     n = dy2d.shape[1]
     lib = _lib.load()
@@ -105,6 +125,8 @@ def embedding_wgrad(idx: torch.Tensor, dout: torch.Tensor, vocab: int, padding_i
     E = dout.shape[-1]
     d2 = dout.reshape(-1, E).contiguous()
     T = d2.shape[0]
+    if idx.dtype != torch.int64:  # nn.Embedding takes int32 ids too; psf_embed_tokens_bwd_f32 reads ``const int64_t*``
+        idx = idx.to(torch.int64)
     if vocab > EMB_MAX_VOCAB or E > EMB_MAX_WIDTH or dout.dtype != torch.float32 or T == 0:
         if dout.is_cuda and torch.cuda.is_current_stream_capturing():
             # aten::embedding_dense_backward sizes a rocprim partition from a host read-back: not capturable, and a
@@ -208,6 +230,8 @@ class TokenLinear(nn.Linear):
     """Drop-in ``nn.Linear`` (``isinstance(layer, nn.Linear)`` holds; identical parameters and state_dict)."""
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if autocast_on(x):  # nn.Linear itself: the dtype, values and gradients autocast gives the stock module
+            return super().forward(x)
         if torch.is_grad_enabled() and (self.weight.requires_grad or (self.bias is not None and self.bias.requires_grad)) \
                 and x.dim() >= 2 and wgrad_supported(x.reshape(-1, x.shape[-1]), self.out_features):
             return _TokenLinearFn.apply(x, self.weight, self.bias)
