@@ -335,6 +335,22 @@ int psf_sum_tensors_bf16(const uint16_t* const* srcs, int32_t count, int64_t n, 
 int psf_adam_step_f32(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                       const int64_t* numels, int32_t count, float lr, float beta1, float beta2, float eps, float step,
                       const float* step_dev, void* stream);
+/*
+ * The same step for bf16 parameters with f32 master weights (the name carries no element-type suffix: the entry takes both).
+ * Per element, with g the bf16 gradient widened to f32 (exact):
+ *     (master, exp_avg, exp_avg_sq) <- the update above on (master, g, exp_avg, exp_avg_sq), in f32 — the f32 kernel's
+ *     arithmetic, one template body;   params_bf16 <- master rounded to nearest even (NaN stays NaN)
+ *   so the bf16 parameter is always the rounded master and never feeds back into the update: at lr = 1e-3 a step moves a
+ *   weight near 1 by a quarter of half a bf16 ulp, which an Adam on the bf16 parameter alone rounds away every time.
+ *   host tables of `count` device pointers: master, exp_avg, exp_avg_sq f32 (4-byte aligned), params_bf16 and grads_bf16
+ *   bf16 as raw bits (2-byte aligned); PSF_E_ALIGN otherwise. The vector path takes a tensor whose f32 arrays are 16-byte
+ *   and whose bf16 arrays are 8-byte aligned with a count that is a multiple of 4; any other tensor takes the scalar path.
+ *   `step` / `step_dev`, the 4096-element chunks, the 40 tensors per launch, the validation in full before the first
+ *   launch and every return code are those of the f32 entry above.
+ */
+int psf_adam_step_master(float* const* master, uint16_t* const* params_bf16, const uint16_t* const* grads_bf16,
+                         float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numels, int32_t count, float lr,
+                         float beta1, float beta2, float eps, float step, const float* step_dev, void* stream);
 
 /*
  * Token embedding fused with the positional-embedding add — the first two lines of PSFNet.forward
@@ -345,6 +361,14 @@ int psf_adam_step_f32(float* const* params, const float* const* grads, float* co
  */
 int psf_embed_tokens_f32(const int64_t* idx, const float* table, const float* pos, float* out, int64_t T, int64_t N,
                          int32_t V, int32_t E, void* stream);
+/*
+ * The same pass on bf16 (raw bits): table [V,E], pos [N,E] or NULL, out [T,E] bf16.
+ *     out[t,:] = rne_bf16(f32(table[idx[t],:]) + f32(pos[t mod N,:]))
+ *   — the bits of the stock `embedding(idx) + pos.unsqueeze(0)` on bf16 tensors. A 16-byte vector holds 8 channels: E a
+ *   positive multiple of 8 (PSF_E_SHAPE); table, pos, out 16-byte aligned (PSF_E_ALIGN). Ids are clamped as above.
+ */
+int psf_embed_tokens_bf16(const int64_t* idx, const uint16_t* table, const uint16_t* pos, uint16_t* out, int64_t T, int64_t N,
+                          int32_t V, int32_t E, void* stream);
 /*
  * Rows of a narrow affine input layer — `init_linear` of the synthetic PSFNet (SyntheticExperiments/psf.py:153-154:
  * Linear(2, embedding_size) on [value, marker]):
@@ -365,6 +389,15 @@ int psf_affine_rows_f32(const float* x, const float* W, const float* bias, float
 int64_t psf_embed_tokens_bwd_workspace(int64_t T, int32_t V, int32_t E);
 int psf_embed_tokens_bwd_f32(const int64_t* idx, const float* dOut, int64_t T, int32_t V, int32_t E, float* dTable,
                              void* workspace, int64_t workspace_bytes, void* stream);
+/*
+ * bf16 dOut [T,E] and bf16 dTable [V,E] (raw bits, 2-byte aligned: PSF_E_ALIGN otherwise). dOut is widened at the load, the
+ * partial sums and the workspace (the same psf_embed_tokens_bwd_workspace bytes) stay f32, and the total is rounded to
+ * nearest even once at the store — the same kernels instantiated for the element type, so
+ *     dTable == rne_bf16(what psf_embed_tokens_bwd_f32 returns for the widened dOut),   bit for bit.
+ * Same limits, deterministic, no atomics, no host read-back, capturable.
+ */
+int psf_embed_tokens_bwd_bf16(const int64_t* idx, const uint16_t* dOut, int64_t T, int32_t V, int32_t E, uint16_t* dTable,
+                              void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * The FLATTEN head of PSFNet, `final = nn.Linear(n_vec * n_channels_V, n_class)` on V.view(B, -1)

@@ -18,6 +18,30 @@ MAX_LINKS = 64
 c_i32, c_i64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
 _I64P = ctypes.POINTER(c_i64)
 
+
+
+class DeviceAddr:
+    """argtype of a device address (an int, or None for NULL) at a position whose element type is NOT the one the entry's name
+    ends in — ``const int64_t* idx`` and ``void* workspace`` of a ``_bf16`` entry — or of an entry whose name ends in no type
+    at all (psf_adam_step_master takes f32 and bf16 arrays). A plain ``c_void_p`` position is read as "a tensor of the suffix's
+    dtype" by whoever checks dtypes at this boundary (tests/ptr_audit.py); these positions are typed by the wrapper that fills
+    them (``token_linear.embedding_wgrad`` allocates them, ``train.ChunkedAdam`` checks every state tensor's dtype)."""
+
+    @classmethod
+    def from_param(cls, value):
+        return value if isinstance(value, ctypes.c_void_p) else ctypes.c_void_p(value)
+
+
+class DeviceAddrTable:
+    """argtype of a host table of device addresses, a ``(c_void_p * n)`` array or None, where ``DeviceAddr`` applies."""
+
+    @classmethod
+    def from_param(cls, value):
+        return ctypes.c_void_p(None) if value is None else value
+
+
+_DA, _DAT = DeviceAddr, DeviceAddrTable
+
 # name -> argtypes (all return int unless noted); mirrors include/psf_chord.h exactly
 _STEP = [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_i64, _I64P, c_vp]
 _BWD = [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_i64, _I64P, c_vp]
@@ -52,12 +76,17 @@ SIGNATURES = {
     "psf_linear_wgrad_strided_f32": ([c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),
     "psf_adam_step_f32": ([ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), _I64P, c_i32,
                            ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp, c_vp], ctypes.c_int),
+    # f32 master weights for bf16 parameters: (master, params_bf16, grads_bf16, exp_avg, exp_avg_sq) pointer tables
+    "psf_adam_step_master": ([_DAT, _DAT, _DAT, _DAT, _DAT, _I64P, c_i32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                              ctypes.c_float, ctypes.c_float, _DA, _DA], ctypes.c_int),
     "psf_sum_tensors_f32": ([ctypes.POINTER(c_vp), c_i32, c_i64, c_vp, c_vp], ctypes.c_int),
     "psf_sum_tensors_bf16": ([ctypes.POINTER(c_vp), c_i32, c_i64, c_vp, c_vp], ctypes.c_int),
     "psf_embed_tokens_f32": ([c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp], ctypes.c_int),
+    "psf_embed_tokens_bf16": ([_DA, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp], ctypes.c_int),  # (idx is int64)
     "psf_affine_rows_f32": ([c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp], ctypes.c_int),
     "psf_embed_tokens_bwd_workspace": ([c_i64, c_i32, c_i32], c_i64),
     "psf_embed_tokens_bwd_f32": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),
+    "psf_embed_tokens_bwd_bf16": ([_DA, c_vp, c_i64, c_i32, c_i32, c_vp, _DA, c_i64, c_vp], ctypes.c_int),  # (idx int64, f32 workspace)
     "psf_flat_head_workspace": ([c_i32, c_i64, c_i32], c_i64),
     "psf_flat_head_f32": ([c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_i64, c_vp], ctypes.c_int),
     "psf_flat_head_bwd_f32": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp], ctypes.c_int),

@@ -7,6 +7,9 @@
 // B = 64: a 6-row table looked up a million times) followed by a broadcast add that re-reads and re-writes the
 // same 84 MB. Here one pass: 16 bytes per thread, the index and table row come from cache, the output is written
 // once. HBM-bound on the output (4*E bytes per token).
+//
+// Both the pass and the table gradient below have a bf16 instance (psf_embed_tokens_bf16, psf_embed_tokens_bwd_bf16): bf16
+// storage, f32 arithmetic, one rounding per element.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -53,6 +56,51 @@ extern "C" int psf_embed_tokens_f32(const int64_t* idx, const float* table, cons
   const int grid = (int)(blocks < 8192 ? blocks : 8192);
   hipLaunchKernelGGL(embed_tokens_k, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), idx, table, pos, out, T, N,
                      V, E / 4);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PSF_OK : psf_internal_fail((int)e, hipGetErrorString(e));
+}
+
+// bf16 table, pos and out: 8 channels per 16-byte vector; table + pos is one f32 add rounded to nearest even once, which are
+// the bits of the stock bf16 `embedding(idx) + pos.unsqueeze(0)` (a bf16 add there is the f32 sum, rounded).
+namespace {
+
+using Bf16x8 = __bf16 __attribute__((ext_vector_type(8)));
+
+__global__ void __launch_bounds__(256)
+embed_tokens_bf16_k(const int64_t* __restrict__ idx, const __bf16* __restrict__ table, const __bf16* __restrict__ pos,
+                    __bf16* __restrict__ out, int64_t T, int64_t N, int32_t V, int32_t E8) {
+  const int64_t total = T * E8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t t = i / E8;
+    const int e8 = (int)(i - t * E8);
+    int64_t v = idx[t];
+    v = v < 0 ? 0 : (v >= V ? V - 1 : v);  // as embed_tokens_k: never a read outside the table
+    Bf16x8 r = reinterpret_cast<const Bf16x8*>(table)[v * E8 + e8];
+    if (pos) {
+      const Bf16x8 p = reinterpret_cast<const Bf16x8*>(pos)[(t % N) * E8 + e8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) r[e] = (__bf16)__fadd_rn((float)r[e], (float)p[e]);
+    }
+    reinterpret_cast<Bf16x8*>(out)[i] = r;
+  }
+}
+
+}  // namespace
+
+extern "C" int psf_embed_tokens_bf16(const int64_t* idx, const uint16_t* table, const uint16_t* pos, uint16_t* out, int64_t T,
+                                     int64_t N, int32_t V, int32_t E, void* stream) {
+  if (!idx || !table || !out) return psf_internal_fail(PSF_E_NULL, "psf_embed_tokens_bf16: idx, table and out must be non-NULL");
+  if (T < 0 || N < 1 || V < 1 || E < 8 || (E & 7)) return psf_internal_fail(PSF_E_SHAPE, "psf_embed_tokens_bf16: need T >= 0, N >= 1, V >= 1, E a positive multiple of 8");
+  if ((reinterpret_cast<uintptr_t>(table) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) ||
+      (pos && (reinterpret_cast<uintptr_t>(pos) & 15)) || (reinterpret_cast<uintptr_t>(idx) & 7))
+    return psf_internal_fail(PSF_E_ALIGN, "psf_embed_tokens_bf16: table, pos and out must be 16-byte aligned, idx 8-byte aligned");
+  if (T == 0) return PSF_OK;
+  const int64_t total = T * (E / 8);
+  const int64_t blocks = (total + 255) / 256;
+  const int grid = (int)(blocks < 8192 ? blocks : 8192);
+  hipLaunchKernelGGL(embed_tokens_bf16_k, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), idx,
+                     reinterpret_cast<const __bf16*>(table), reinterpret_cast<const __bf16*>(pos), reinterpret_cast<__bf16*>(out), T, N,
+                     V, E / 8);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? PSF_OK : psf_internal_fail((int)e, hipGetErrorString(e));
 }
@@ -121,9 +169,12 @@ namespace {
 constexpr int kEmbSlicesMax = 2048;
 constexpr int kEmbTokensPerSlice = 128;
 
-__global__ void __launch_bounds__(64)
-embed_bwd_partial_k(const int64_t* __restrict__ idx, const float* __restrict__ dOut, int64_t T, int32_t V, int32_t E,
-                    int32_t ep_log2, int64_t tokens_per_slice, float* __restrict__ part) {
+// One body for both element types of dOut (float, __bf16): a bf16 gradient is widened at the load (exact), everything behind
+// the load — the walk, the LDS tables, the slice rule, the f32 partial sums — is the same code.
+template <typename TIn>
+__device__ __forceinline__ void embed_bwd_partial_body(const int64_t* __restrict__ idx, const TIn* __restrict__ dOut, int64_t T,
+                                                       int32_t V, int32_t E, int32_t ep_log2, int64_t tokens_per_slice,
+                                                       float* __restrict__ part) {
   extern __shared__ float tab[];  // [subs][V][ep], subs * ep == 64
   const int lane = threadIdx.x;
   const int ep = 1 << ep_log2, subs = 64 >> ep_log2;
@@ -145,7 +196,7 @@ embed_bwd_partial_k(const int64_t* __restrict__ idx, const float* __restrict__ d
       int64_t vv = ok ? idx[tu] : 0;
       vv = vv < 0 ? 0 : (vv >= V ? V - 1 : vv);
       v[u] = (int)vv;
-      g[u] = (ok && active) ? dOut[tu * E + c] : 0.f;
+      g[u] = (ok && active) ? (float)dOut[tu * E + c] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) mine[v[u] * ep] += g[u];  // in token order; a single wave's LDS accesses stay ordered
@@ -163,12 +214,26 @@ embed_bwd_partial_k(const int64_t* __restrict__ idx, const float* __restrict__ d
   }
 }
 
+__global__ void __launch_bounds__(64)
+embed_bwd_partial_k(const int64_t* __restrict__ idx, const float* __restrict__ dOut, int64_t T, int32_t V, int32_t E,
+                    int32_t ep_log2, int64_t tokens_per_slice, float* __restrict__ part) {
+  embed_bwd_partial_body<float>(idx, dOut, T, V, E, ep_log2, tokens_per_slice, part);
+}
+
+__global__ void __launch_bounds__(64)
+embed_bwd_partial_bf16_k(const int64_t* __restrict__ idx, const __bf16* __restrict__ dOut, int64_t T, int32_t V, int32_t E,
+                         int32_t ep_log2, int64_t tokens_per_slice, float* __restrict__ part) {
+  embed_bwd_partial_body<__bf16>(idx, dOut, T, V, E, ep_log2, tokens_per_slice, part);
+}
+
 // dTable[i] = sum over the slices of part[q][i]. A workgroup owns 32 consecutive elements; its 32 slice lanes each add
 // every 32nd slice in ascending order, then the 32 sub-sums are added in lane order: a fixed association. (With one
-// thread per element the 192 outputs of Temporal Order took 235 us for 1024 dependent loads each.)
+// thread per element the 192 outputs of Temporal Order took 235 us for 1024 dependent loads each.) TOut = __bf16 rounds
+// the f32 total once, at the store.
 constexpr int kEmbRedLanes = 32;
-__global__ void __launch_bounds__(32 * kEmbRedLanes)
-embed_bwd_reduce_k(const float* __restrict__ part, int32_t slices, int64_t n, float* __restrict__ dTable) {
+template <typename TOut>
+__device__ __forceinline__ void embed_bwd_reduce_body(const float* __restrict__ part, int32_t slices, int64_t n,
+                                                      TOut* __restrict__ dTable) {
   __shared__ float sub[kEmbRedLanes][32];
   const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
   const int64_t i = (int64_t)blockIdx.x * 32 + e;
@@ -181,8 +246,18 @@ embed_bwd_reduce_k(const float* __restrict__ part, int32_t slices, int64_t n, fl
     float tot = sub[0][e];
 #pragma unroll
     for (int q = 1; q < kEmbRedLanes; ++q) tot += sub[q][e];
-    dTable[i] = tot;
+    dTable[i] = (TOut)tot;
   }
+}
+
+__global__ void __launch_bounds__(32 * kEmbRedLanes)
+embed_bwd_reduce_k(const float* __restrict__ part, int32_t slices, int64_t n, float* __restrict__ dTable) {
+  embed_bwd_reduce_body<float>(part, slices, n, dTable);
+}
+
+__global__ void __launch_bounds__(32 * kEmbRedLanes)
+embed_bwd_reduce_bf16_k(const float* __restrict__ part, int32_t slices, int64_t n, __bf16* __restrict__ dTable) {
+  embed_bwd_reduce_body<__bf16>(part, slices, n, dTable);
 }
 
 int emb_slices(int64_t T) {
@@ -197,12 +272,20 @@ extern "C" int64_t psf_embed_tokens_bwd_workspace(int64_t T, int32_t V, int32_t 
   return (int64_t)emb_slices(T) * V * E * (int64_t)sizeof(float);
 }
 
-extern "C" int psf_embed_tokens_bwd_f32(const int64_t* idx, const float* dOut, int64_t T, int32_t V, int32_t E,
-                                        float* dTable, void* workspace, int64_t workspace_bytes, void* stream) {
+namespace {
+
+// The host side of both entries: PK / RK are the partial and reduce kernels of the element types.
+template <typename TIn, typename TOut, typename PK, typename RK>
+int embed_bwd_launch(PK partial_k, RK reduce_k, const int64_t* idx, const TIn* dOut, int64_t T, int32_t V, int32_t E, TOut* dTable,
+                     void* workspace, int64_t workspace_bytes, void* stream) {
   if (!idx || !dOut || !dTable || !workspace) return psf_internal_fail(PSF_E_NULL, "psf_embed_tokens_bwd: NULL argument");
   const int64_t need = psf_embed_tokens_bwd_workspace(T, V, E);
   if (need < 0) return psf_internal_fail(PSF_E_SHAPE, "psf_embed_tokens_bwd: need T >= 1, 1 <= V <= 512, 1 <= E <= 4096");
   if (workspace_bytes < need) return psf_internal_fail(PSF_E_SHAPE, "psf_embed_tokens_bwd: workspace smaller than psf_embed_tokens_bwd_workspace(T, V, E)");
+  if constexpr (sizeof(TIn) == 2) {  // (the f32 entry checks what it always checked)
+    if ((reinterpret_cast<uintptr_t>(dOut) | reinterpret_cast<uintptr_t>(dTable)) & 1)
+      return psf_internal_fail(PSF_E_ALIGN, "psf_embed_tokens_bwd_bf16: dOut and dTable must be 2-byte aligned");
+  }
   const int slices = emb_slices(T);
   const int64_t tps = (T + slices - 1) / slices;
   int ep_log2 = 6;  // columns per sub-table: E rounded up to a power of two, at most 64
@@ -211,12 +294,25 @@ extern "C" int psf_embed_tokens_bwd_f32(const int64_t* idx, const float* dOut, i
   const size_t lds = (size_t)V * 64 * sizeof(float);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipError_t e = hipSuccess;
-  if (lds > 48 * 1024) e = hipFuncSetAttribute((const void*)embed_bwd_partial_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 48 * 1024) e = hipFuncSetAttribute((const void*)partial_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return psf_internal_fail((int)e, hipGetErrorString(e));
   float* part = reinterpret_cast<float*>(workspace);
-  hipLaunchKernelGGL(embed_bwd_partial_k, dim3(slices, chunks), dim3(64), lds, s, idx, dOut, T, V, E, ep_log2, tps, part);
+  hipLaunchKernelGGL(partial_k, dim3(slices, chunks), dim3(64), lds, s, idx, dOut, T, V, E, ep_log2, tps, part);
   const int64_t n = (int64_t)V * E;
-  hipLaunchKernelGGL(embed_bwd_reduce_k, dim3((unsigned)((n + 31) / 32)), dim3(32 * kEmbRedLanes), 0, s, part, slices, n, dTable);
+  hipLaunchKernelGGL(reduce_k, dim3((unsigned)((n + 31) / 32)), dim3(32 * kEmbRedLanes), 0, s, (const float*)part, slices, n, dTable);
   e = hipGetLastError();
   return e == hipSuccess ? PSF_OK : psf_internal_fail((int)e, hipGetErrorString(e));
+}
+
+}  // namespace
+
+extern "C" int psf_embed_tokens_bwd_f32(const int64_t* idx, const float* dOut, int64_t T, int32_t V, int32_t E,
+                                        float* dTable, void* workspace, int64_t workspace_bytes, void* stream) {
+  return embed_bwd_launch(embed_bwd_partial_k, embed_bwd_reduce_k, idx, dOut, T, V, E, dTable, workspace, workspace_bytes, stream);
+}
+
+extern "C" int psf_embed_tokens_bwd_bf16(const int64_t* idx, const uint16_t* dOut, int64_t T, int32_t V, int32_t E,
+                                         uint16_t* dTable, void* workspace, int64_t workspace_bytes, void* stream) {
+  return embed_bwd_launch(embed_bwd_partial_bf16_k, embed_bwd_reduce_bf16_k, idx, reinterpret_cast<const __bf16*>(dOut), T, V, E,
+                          reinterpret_cast<__bf16*>(dTable), workspace, workspace_bytes, stream);
 }

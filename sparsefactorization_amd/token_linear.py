@@ -116,18 +116,29 @@ class _TokenLinearFn(torch.autograd.Function):
 
 EMB_MAX_VOCAB, EMB_MAX_WIDTH = 512, 4096  # limits of psf_embed_tokens_bwd_f32
 
+# "never" (default) or "always": whether bf16 token embeddings run on the library's bf16 instances — the lookup fused with the
+# positional add on psf_embed_tokens_bf16 (the bits of the stock `embedding(idx) + pos` in bf16) and the table gradient on
+# psf_embed_tokens_bwd_bf16 (f32 partial sums, one rounding: capturable, unlike aten::embedding_dense_backward) — instead of
+# the stock nn.Embedding path. "always" is what makes a bf16 token model capturable by train.GraphedStep; opt-in like
+# chord.bf16_chain_bwd_route, because the table gradient then differs from the stock operator's in its summation order
+# (profiles/bf16_train_graph_ab.md). At "never" nothing here is reached.
+bf16_route = "never"
+
 
 def embedding_wgrad(idx: torch.Tensor, dout: torch.Tensor, vocab: int, padding_idx) -> torch.Tensor:
     """d(table) [vocab, E] of ``table[idx]`` given d(out) [..., E]: ``psf_embed_tokens_bwd_f32`` (csrc/embed.hip —
     per-slice LDS tables with single-owner accumulation, fixed-order reduction: deterministic, no host read-back, so
     a training step stays capturable in a HIP graph). Vocabularies beyond its LDS table use PyTorch's kernel — in
-    eager mode only: under stream capture that case raises (the aten operator is not capturable)."""
+    eager mode only: under stream capture that case raises (the aten operator is not capturable). A bf16 ``dout`` goes to
+    ``psf_embed_tokens_bwd_bf16`` (same kernels, f32 partial sums, a bf16 table gradient rounded once) when ``bf16_route`` is
+    "always", and through the aten operator otherwise."""
     E = dout.shape[-1]
     d2 = dout.reshape(-1, E).contiguous()
     T = d2.shape[0]
     if idx.dtype != torch.int64:  # nn.Embedding takes int32 ids too; psf_embed_tokens_bwd_f32 reads ``const int64_t*``
         idx = idx.to(torch.int64)
-    if vocab > EMB_MAX_VOCAB or E > EMB_MAX_WIDTH or dout.dtype != torch.float32 or T == 0:
+    bf16 = dout.dtype == torch.bfloat16 and bf16_route == "always" and dout.is_cuda
+    if vocab > EMB_MAX_VOCAB or E > EMB_MAX_WIDTH or not (dout.dtype == torch.float32 or bf16) or T == 0:
         if dout.is_cuda and torch.cuda.is_current_stream_capturing():
             # aten::embedding_dense_backward sizes a rocprim partition from a host read-back: not capturable, and a
             # replay of such a capture faulted the GPU (profiles/r01_graph_step_lab.log). Refuse instead.
@@ -141,11 +152,12 @@ def embedding_wgrad(idx: torch.Tensor, dout: torch.Tensor, vocab: int, padding_i
     idx_c = idx.reshape(-1).contiguous()
     ws_bytes = lib.psf_embed_tokens_bwd_workspace(T, vocab, E)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=d2.device)
-    dW = torch.empty((vocab, E), dtype=torch.float32, device=d2.device)
+    dW = torch.empty((vocab, E), dtype=dout.dtype, device=d2.device)
+    entry, name = ((lib.psf_embed_tokens_bwd_bf16, "psf_embed_tokens_bwd_bf16") if bf16
+                   else (lib.psf_embed_tokens_bwd_f32, "psf_embed_tokens_bwd_f32"))
     with torch.cuda.device(d2.device):
-        rc = lib.psf_embed_tokens_bwd_f32(idx_c.data_ptr(), d2.data_ptr(), T, vocab, E, dW.data_ptr(), ws.data_ptr(),
-                                          ws_bytes, _lib.stream_ptr(d2.device))
-    _lib.check(rc, "psf_embed_tokens_bwd_f32")
+        rc = entry(idx_c.data_ptr(), d2.data_ptr(), T, vocab, E, dW.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(d2.device))
+    _lib.check(rc, name)
     if padding_idx is not None and padding_idx >= 0:
         dW[padding_idx].zero_()
     return dW
@@ -178,12 +190,14 @@ class _EmbedTokensFn(torch.autograd.Function):
         idx_c = idx.contiguous()
         T = idx_c.numel()
         N = pos.shape[0] if pos is not None else 1
-        out = torch.empty(*idx.shape, E, dtype=torch.float32, device=idx.device)
+        out = torch.empty(*idx.shape, E, dtype=weight.dtype, device=idx.device)
         w, p = weight.detach().contiguous(), (pos.detach().contiguous() if pos is not None else None)
+        entry, name = ((lib.psf_embed_tokens_bf16, "psf_embed_tokens_bf16") if weight.dtype == torch.bfloat16
+                       else (lib.psf_embed_tokens_f32, "psf_embed_tokens_f32"))
         with torch.cuda.device(idx.device):
-            rc = lib.psf_embed_tokens_f32(idx_c.data_ptr(), w.data_ptr(), p.data_ptr() if p is not None else None,
-                                          out.data_ptr(), T, N, V, E, _lib.stream_ptr(idx.device))
-        _lib.check(rc, "psf_embed_tokens_f32")
+            rc = entry(idx_c.data_ptr(), w.data_ptr(), p.data_ptr() if p is not None else None, out.data_ptr(), T, N, V, E,
+                       _lib.stream_ptr(idx.device))
+        _lib.check(rc, name)
         ctx.save_for_backward(idx_c)
         ctx.vocab, ctx.padding_idx, ctx.has_pos, ctx.n_pos = V, padding_idx, pos is not None, N
         return out
@@ -200,11 +214,22 @@ class _EmbedTokensFn(torch.autograd.Function):
         return None, dW, dpos, None
 
 
+def _vec16(t: torch.Tensor) -> bool:
+    """What psf_embed_tokens_bf16 reads as it stands (a non-contiguous operand is copied, and a copy is aligned)."""
+    return not t.is_contiguous() or t.data_ptr() % 16 == 0
+
+
 def embed_tokens(idx: torch.Tensor, embedding: nn.Embedding, pos: torch.Tensor = None) -> torch.Tensor:
     """``embedding(idx) + pos.unsqueeze(0)`` (``pos`` [N, E] with N = idx.shape[-1], or None) — the opening lines of
     every PSFNet.forward. One fused pass on the GPU for plain fp32 embeddings; anything else (CPU, max_norm, sparse
-    gradients, E not a multiple of 4) takes the stock modules."""
+    gradients, E not a multiple of 4) takes the stock modules. bf16 tables take the pass too when ``bf16_route`` is "always"
+    (``pos`` bf16 or None, E a multiple of 8, 16-byte aligned storage), and the stock modules otherwise."""
     w = embedding.weight
+    if (bf16_route == "always" and idx.is_cuda and idx.dtype == torch.int64 and w.dtype == torch.bfloat16 and w.shape[1] % 8 == 0
+            and embedding.max_norm is None and not embedding.scale_grad_by_freq and not embedding.sparse
+            and _vec16(w) and (pos is None or (pos.dtype == torch.bfloat16 and pos.dim() == 2 and pos.shape[0] == idx.shape[-1]
+                                               and pos.shape[1] == w.shape[1] and _vec16(pos)))):
+        return _EmbedTokensFn.apply(idx, w, pos, embedding.padding_idx)
     if (idx.is_cuda and idx.dtype == torch.int64 and w.dtype == torch.float32 and w.shape[1] % 4 == 0
             and embedding.max_norm is None and not embedding.scale_grad_by_freq and not embedding.sparse
             and (pos is None or (pos.dtype == torch.float32 and pos.dim() == 2 and pos.shape[0] == idx.shape[-1]
@@ -219,7 +244,8 @@ class TokenEmbedding(nn.Embedding):
     at ~1e6 positions; larger vocabularies, CPU tensors and exotic options use the stock path."""
 
     def forward(self, idx: torch.Tensor) -> torch.Tensor:
-        if (torch.is_grad_enabled() and self.weight.requires_grad and idx.is_cuda and self.weight.dtype == torch.float32
+        if (torch.is_grad_enabled() and self.weight.requires_grad and idx.is_cuda
+                and (self.weight.dtype == torch.float32 or (self.weight.dtype == torch.bfloat16 and bf16_route == "always"))
                 and self.num_embeddings <= EMB_MAX_VOCAB and self.embedding_dim <= EMB_MAX_WIDTH
                 and self.max_norm is None and not self.scale_grad_by_freq and not self.sparse):
             return _TokenEmbeddingFn.apply(idx, self.weight, self.padding_idx)

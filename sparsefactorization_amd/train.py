@@ -88,6 +88,14 @@ class ChunkedAdam(torch.optim.Optimizer):
     ``load_state_dict`` / ``torch.save`` work as for any optimizer (the host-side launch plan — ctypes pointer tables —
     lives outside ``param_groups`` and is rebuilt whenever a parameter, a gradient set or a state tensor changes address).
 
+    bfloat16 parameters are stepped with f32 master weights on ``psf_adam_step_master``: their state is ``master`` (f32,
+    ``p.float()`` at the first step), ``exp_avg`` and ``exp_avg_sq`` (both f32) and ``step``; the update runs on the master
+    from the widened bf16 gradient and the parameter is rewritten as the master rounded to nearest even. (Without a master the
+    parameter would not train: at lr = 1e-3 a step moves a weight near 1 by 1e-3, and half a bf16 ulp there is 3.9e-3.) f32 and
+    bf16 parameters of one group share the group's step counter. Any other dtype is a TypeError at construction.
+    ``load_state_dict`` puts the f32 state of a bf16 parameter back as f32 with its saved bits (torch's casts every floating
+    state tensor to the parameter's dtype).
+
     ``capturable``: ``step`` is ONE device scalar shared by all parameters of a group (advanced by a one-element kernel,
     read by the update kernel), so a captured step can be replayed. That is torch's Adam as long as every parameter that
     ever gets a gradient gets one on EVERY step (PSFNet: parameters the forward does not use never get one and are simply
@@ -95,9 +103,16 @@ class ChunkedAdam(torch.optim.Optimizer):
     correction, so that raises instead. A non-capturable instance raises when stepped under stream capture (the host step
     count would be baked into the graph), like torch's Adam."""
 
+    MASTER_STATE = ("master", "exp_avg", "exp_avg_sq")  # the f32 state tensors of a bf16 parameter
+
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, capturable: bool = False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, capturable=capturable))
-        self._plans: Dict[int, tuple] = {}       # group index -> (key, pointer tables..., states)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.dtype not in (torch.float32, torch.bfloat16):
+                    raise TypeError(f"ChunkedAdam steps float32 parameters and bfloat16 parameters (with f32 master weights); "
+                                    f"got a {p.dtype} parameter of shape {tuple(p.shape)}")
+        self._plans: Dict[int, tuple] = {}       # group index -> (key, per-dtype pointer tables, states)
         self._step_devs: Dict[int, torch.Tensor] = {}  # group index -> the shared device step counter (capturable)
         self._cap_live: Dict[int, tuple] = {}    # group index -> ids of the parameters the shared counter counts for
         self._live_states: Dict[int, tuple] = {}  # group index -> (ids of the parameters with a gradient, their state dicts)
@@ -108,6 +123,18 @@ class ChunkedAdam(torch.optim.Optimizer):
         self._step_devs.clear()
         self._cap_live.clear()
         self._live_states.clear()
+        # torch's load_state_dict has cast every floating state tensor to its parameter's dtype: the f32 master and moments of
+        # a bf16 parameter came back as bf16. Put them back from the saved tensors, as f32 with their saved bits.
+        saved_state = state_dict["state"]
+        for saved_group, group in zip(state_dict["param_groups"], self.param_groups):
+            for key, p in zip(saved_group["params"], group["params"]):
+                st = self.state.get(p)
+                if p.dtype != torch.bfloat16 or not st or key not in saved_state:
+                    continue
+                for name in self.MASTER_STATE:
+                    v = saved_state[key].get(name)
+                    if torch.is_tensor(v):
+                        st[name] = v.detach().to(device=p.device, dtype=torch.float32, copy=True)
         for gi, group in enumerate(self.param_groups):  # re-link the loaded per-parameter counters to ONE device scalar
             if not group["capturable"]:
                 for p in group["params"]:
@@ -131,12 +158,39 @@ class ChunkedAdam(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none: bool = True):
         """As torch's (gradients dropped, not zeroed, by default) without its per-call bookkeeping: 75 -> 15 us of host time
-        per step on a 50-tensor model, where the host is the bound (profiles/lra_host_profile.py)."""
+        per step on a 50-tensor model, where the host is the bound (profiles/lra_host_profile.py). Gradients of either
+        dtype; the f32 state of a bf16 parameter is not a gradient and stays."""
         if not set_to_none:
             return super().zero_grad(set_to_none=False)
         for group in self.param_groups:
             for p in group["params"]:
                 p.grad = None
+
+    @staticmethod
+    def _build_plan(key, live, states):
+        """Pointer tables per entry: the f32 parameters for psf_adam_step_f32, the bf16 ones (master, parameter, moments) for
+        psf_adam_step_master. Each part: (master?, positions in ``live``, tables in the entry's order before / after the
+        gradient table, element counts)."""
+        import ctypes
+        parts = []
+        for master in (False, True):
+            pos = [i for i, p in enumerate(live) if (p.dtype == torch.bfloat16) == master]
+            if not pos:
+                continue
+            n = len(pos)
+            tab = lambda ts: (ctypes.c_void_p * n)(*[x.data_ptr() for x in ts])  # noqa: E731
+            for i in pos:
+                for name in (ChunkedAdam.MASTER_STATE if master else ChunkedAdam.MASTER_STATE[1:]):
+                    t = states[i].get(name)
+                    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != live[i].numel() or not t.is_contiguous():
+                        raise RuntimeError(f"ChunkedAdam: state '{name}' of a {live[i].dtype} parameter must be a contiguous float32 "
+                                           f"tensor of its size; got {getattr(t, 'dtype', type(t))}")
+            ps = [live[i] for i in pos]
+            head = [tab([states[i]["master"] for i in pos]), tab(ps)] if master else [tab(ps)]
+            tail = [tab([states[i]["exp_avg"] for i in pos]), tab([states[i]["exp_avg_sq"] for i in pos]),
+                    (ctypes.c_int64 * n)(*[p.numel() for p in ps])]
+            parts.append((master, pos, head, tail))
+        return (key, parts, states)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -174,8 +228,9 @@ class ChunkedAdam(torch.optim.Optimizer):
             live_ids = tuple(map(id, live))
             seen = self._live_states.get(gi)
             # (every entry re-validated by identity — 8 us for 60 parameters: a user who clears, deletes or replaces ONE
-            # parameter's state between steps, `opt.state[p].clear()` / `del opt.state[p]`, gets fresh moments for it, and
-            # no update ever lands in a dict that self.state no longer holds)
+            # parameter's state between steps, `opt.state[p].clear()` / `del opt.state[p]`, gets fresh moments for it — and,
+            # for a bf16 parameter, a fresh master from the parameter as it stands — and no update ever lands in a dict that
+            # self.state no longer holds)
             if (seen is not None and seen[0] == live_ids
                     and all(st and self.state.get(p) is st for p, st in zip(live, seen[1]))):
                 states = seen[1]
@@ -184,57 +239,62 @@ class ChunkedAdam(torch.optim.Optimizer):
                     st = self.state[p]
                     if not st:
                         st["step"] = self._step_devs[gi] if cap else 0.0
-                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                        # (bf16 parameters: f32 moments, and the f32 master the update runs on)
+                        st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.preserve_format)
+                        st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.preserve_format)
+                    if p.dtype == torch.bfloat16 and "master" not in st:
+                        st["master"] = p.detach().float()
                 states = [self.state[p] for p in live]
                 self._live_states[gi] = (live_ids, states)
             # host-side plan (pointer tables of the parameters and their moments), rebuilt only when a tensor of it
             # moved: the small LRA models are launch-bound, every microsecond here counts
-            key = tuple([(p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()) for p, st in zip(live, states)])
+            key = tuple([(p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                          st["master"].data_ptr() if p.dtype == torch.bfloat16 else 0) for p, st in zip(live, states)])
             plan = self._plans.get(gi)
             if plan is None or plan[0] != key:
-                n = len(live)
-                tab = lambda ts: (ctypes.c_void_p * n)(*[x.data_ptr() for x in ts])  # noqa: E731
-                plan = (key, tab(live), tab([st["exp_avg"] for st in states]), tab([st["exp_avg_sq"] for st in states]),
-                        (ctypes.c_int64 * n)(*[p.numel() for p in live]), states)
-                self._plans[gi] = plan
-            _, ptab, mtab, vtab, sizes, _ = plan
-            n = len(live)
+                plan = self._plans[gi] = self._build_plan(key, live, states)
+            parts = plan[1]
             grads = [g if g.is_contiguous() else g.contiguous() for g in grads]  # (copies stay alive until the launch is queued)
-            gtab = (ctypes.c_void_p * n)(*[g.data_ptr() for g in grads])
             b1, b2 = group["betas"]
+            hyper = (group["lr"], b1, b2, group["eps"])
             stream = _lib.stream_ptr(dev)
             with torch.cuda.device(dev):
                 if cap:
                     self._step_devs[gi].add_(1.0)
-                    rc = lib.psf_adam_step_f32(ptab, gtab, mtab, vtab, sizes, n, group["lr"], b1, b2, group["eps"], 1.0,
-                                               self._step_devs[gi].data_ptr(), stream)
+                    t0, step_dev, uniform = 1.0, self._step_devs[gi].data_ptr(), True
                 else:
-                    t0 = states[0]["step"] + 1.0
+                    t0, step_dev = states[0]["step"] + 1.0, None
                     uniform = True
                     for st in states:
                         st["step"] += 1.0
                         uniform = uniform and st["step"] == t0
+                rc = 0
+                for master, pos, head, tail in parts:
+                    n = len(pos)
+                    entry = lib.psf_adam_step_master if master else lib.psf_adam_step_f32
+                    gtab = (ctypes.c_void_p * n)(*[grads[i].data_ptr() for i in pos])
                     if uniform:
-                        rc = lib.psf_adam_step_f32(ptab, gtab, mtab, vtab, sizes, n, group["lr"], b1, b2, group["eps"], t0,
-                                                   None, stream)
-                    else:  # parameters that skipped steps (grad None) have their own count: one call per tensor
-                        rc = 0
-                        for i, st in enumerate(states):
-                            one = lambda tb: (ctypes.c_void_p * 1)(tb[i])  # noqa: E731
-                            rc = rc or lib.psf_adam_step_f32(one(ptab), one(gtab), one(mtab), one(vtab),
-                                                             (ctypes.c_int64 * 1)(sizes[i]), 1, group["lr"], b1, b2,
-                                                             group["eps"], st["step"], None, stream)
-            _lib.check(rc, "psf_adam_step_f32")
+                        rc = rc or entry(*head, gtab, *tail, n, *hyper, t0, step_dev, stream)
+                        continue
+                    # parameters that skipped steps (grad None) have their own count: one call per tensor
+                    for j, i in enumerate(pos):
+                        one = lambda tb: (ctypes.c_void_p * 1)(tb[j])  # noqa: E731
+                        rc = rc or entry(*[one(tb) for tb in head], one(gtab), one(tail[0]), one(tail[1]),
+                                         (ctypes.c_int64 * 1)(tail[2][j]), 1, *hyper, states[i]["step"], None, stream)
+            _lib.check(rc, "psf_adam_step_f32 / psf_adam_step_master")
         return loss
 
 
-def make_adam(params, lr: float, capturable: bool = False) -> torch.optim.Optimizer:
+def make_adam(params, lr: float, capturable: bool = False, master_weights: bool = False) -> torch.optim.Optimizer:
     """``optim.Adam(net.parameters(), lr=...)`` of psf_training.py:50 / listops_training.py:84. On the GPU (contiguous
     fp32 parameters) the same update on ``ChunkedAdam``; otherwise torch's own Adam. ``capturable``: the step counter
-    lives on the device, so the step can be captured in a HIP graph (``GraphedStep``)."""
+    lives on the device, so the step can be captured in a HIP graph (``GraphedStep``). ``master_weights``: contiguous GPU
+    parameters that are float32 or bfloat16 go to ``ChunkedAdam`` too, which steps the bf16 ones on f32 master weights kept in
+    its state (what a bf16 model needs to train at all, and to be captured); with the default False a model with a bf16
+    parameter gets torch's Adam, as before."""
     params = list(params)
-    if params and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in params):
+    dtypes = (torch.float32, torch.bfloat16) if master_weights else (torch.float32,)
+    if params and all(p.is_cuda and p.dtype in dtypes and p.is_contiguous() for p in params):
         return ChunkedAdam(params, lr=lr, capturable=capturable)
     return torch.optim.Adam(params, lr=lr)
 
@@ -313,16 +373,20 @@ def check_capturable(net: torch.nn.Module) -> None:
     """Raise before a capture if a token embedding of ``net`` would send its weight gradient through
     ``aten::embedding_dense_backward``: that operator sizes a rocprim partition from a host read-back, which cannot be
     captured, and REPLAYING such a capture faulted the GPU (profiles/r01_graph_step_lab.log). The capturable kernel,
-    ``psf_embed_tokens_bwd_f32``, holds the table in LDS: vocab <= EMB_MAX_VOCAB, width <= EMB_MAX_WIDTH, fp32."""
+    ``psf_embed_tokens_bwd_f32``, holds the table in LDS: vocab <= EMB_MAX_VOCAB, width <= EMB_MAX_WIDTH, fp32 — or bf16
+    on its bf16 instance when ``token_linear.bf16_route`` is "always"."""
+    from . import token_linear
     from .token_linear import EMB_MAX_VOCAB, EMB_MAX_WIDTH, TokenEmbedding
     for name, m in net.named_modules():
         if isinstance(m, TokenEmbedding) and m.weight.requires_grad:
-            if m.num_embeddings > EMB_MAX_VOCAB or m.embedding_dim > EMB_MAX_WIDTH or m.weight.dtype != torch.float32:
+            dtype_ok = m.weight.dtype == torch.float32 or (m.weight.dtype == torch.bfloat16 and token_linear.bf16_route == "always")
+            if m.num_embeddings > EMB_MAX_VOCAB or m.embedding_dim > EMB_MAX_WIDTH or not dtype_ok:
                 raise RuntimeError(
                     f"GraphedStep: embedding '{name}' ({m.num_embeddings} x {m.embedding_dim}, {m.weight.dtype}) is "
                     f"outside the capturable table-gradient kernel's limits (vocab <= {EMB_MAX_VOCAB}, width <= "
                     f"{EMB_MAX_WIDTH}, float32); its gradient would run on aten::embedding_dense_backward, which cannot "
-                    "be captured in a HIP graph. Train this model eagerly (no --graph).")
+                    "be captured in a HIP graph. Train this model eagerly (no --graph). A bfloat16 table within those "
+                    "limits is capturable with token_linear.bf16_route = \"always\".")
 
 
 class GraphedStep:
@@ -365,7 +429,9 @@ class GraphedStep:
         # the warm-up steps are real optimisation steps; they are undone after the capture (parameters, buffers and
         # optimizer state restored IN PLACE — the graph holds their addresses), so a graphed run starts from the same
         # state, and follows the same trajectory, as an eager one (tests/test_reference_pins.py; with dropout too: the
-        # generator states are put back, and a replay advances the philox offset by what an eager step draws)
+        # generator states are put back, and a replay advances the philox offset by what an eager step draws). State tensors
+        # that the warm-up created go back to what a first step starts from: zero — except ChunkedAdam's f32 ``master`` of a
+        # bf16 parameter, which goes back to the restored parameter's value (the ``finally`` block below).
         with torch.no_grad():
             tensors = list(net.parameters()) + list(net.buffers())
             snapshot = [t.detach().clone() for t in tensors]
@@ -409,7 +475,12 @@ class GraphedStep:
                     before = opt_before.get(id(p), {})
                     for k, v in list(st.items()):
                         if torch.is_tensor(v):
-                            v.copy_(before[k]) if k in before else v.zero_()
+                            if k in before:
+                                v.copy_(before[k])
+                            elif k == "master":  # ChunkedAdam's f32 master of a bf16 parameter, created by the warm-up:
+                                v.copy_(p)       # the value its first step would give it (the parameter, restored above)
+                            else:
+                                v.zero_()
                         elif k == "step":  # a host-side step count (ChunkedAdam, not capturable)
                             st[k] = before.get(k, 0.0)
             torch.set_rng_state(rng_cpu)
