@@ -420,6 +420,26 @@ int psf_flat_head_bwd_f32(const float* dY, const float* X, const float* W, float
                           void* stream);
 int psf_flat_head_f32(const float* X, const float* W, const float* bias, float* out, int32_t B, int64_t K, int32_t J,
                       void* workspace, int64_t workspace_bytes, void* stream);
+/*
+ * The head and its backward on bf16 (raw bits): X, W, bias, out, dY, dX, dW are bf16 arrays of the shapes above. The contract
+ * is the one of psf_embed_tokens_bwd_bf16: operands are widened at the load (exact), everything in between is the f32 kernel's
+ * arithmetic in the f32 kernel's order — the same kernels instantiated for the element type: a thread owns the same four
+ * consecutive K elements (one 8-byte load), the same chunk rule, the same f32 partial sums in the same workspace
+ * (psf_flat_head_workspace bytes, unchanged), the same fixed-order combines, the bias widened and added in f32; the backward
+ * keeps dY widened in LDS, sums dW in f32 over b ascending and dX as the f32 FMA chain over j ascending — and each result
+ * element is rounded to bf16 once, at the store (a plain cast: round to nearest even, a NaN stays a NaN). The product of two
+ * bf16 values is exact in f32, so bit for bit
+ *     out == rne_bf16(what psf_flat_head_f32     returns for the widened X, W, bias)
+ *     dX  == rne_bf16(what psf_flat_head_bwd_f32 returns for the widened dY, X, W)
+ *     dW  == rne_bf16(what psf_flat_head_bwd_f32 returns for the widened dY, X, W)
+ * Limits as in f32: forward 1 <= J <= 8; backward 1 <= J <= 16 and 1 <= B <= 1024; K a positive multiple of 4. X, W, dX, dW
+ * 8-byte aligned (PSF_E_ALIGN otherwise); NULL and shape errors as the f32 entries report them; everything is validated before
+ * the first HIP call. The bias gradient stays with the caller. No atomics, no host read-back: deterministic and capturable.
+ */
+int psf_flat_head_bf16(const uint16_t* X, const uint16_t* W, const uint16_t* bias, uint16_t* out, int32_t B, int64_t K, int32_t J,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int psf_flat_head_bwd_bf16(const uint16_t* dY, const uint16_t* X, const uint16_t* W, uint16_t* dX, uint16_t* dW, int32_t B, int64_t K,
+                           int32_t J, void* stream);
 
 /*
  * Producer side, forward (inference): K two-layer token-wise MLPs sharing one input, fused in one launch —

@@ -7,6 +7,13 @@
 // in registers, each batch row's chunk is read once as 16-byte loads and dotted with all J rows, lane sums are
 // combined by wave shuffles and across the four waves through LDS in a fixed order, and the per-chunk partial sums
 // are added in chunk order by a second tiny kernel (no atomics: bit-reproducible). HBM-bound on X.
+//
+// Every kernel here has a bf16 instance (psf_flat_head_bf16, psf_flat_head_bwd_bf16): one body per element type. A bf16 operand
+// is widened at the load (exact), everything behind the load is the f32 body — the same thread owns the same four consecutive
+// K elements (now one 8-byte load), the same chunk rule, the same f32 partial sums in the same workspace, the same fixed-order
+// combines — and each result element is rounded to nearest even once, at the store. The product of two bf16 values is exact in
+// f32, so the body's fmaf is the f32 kernel's fmaf on the widened values:
+//     bf16 result == rne_bf16(f32 entry on the widened operands), bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,11 +27,42 @@ constexpr int kChunk = 4096;   // floats of K per workgroup at U = 4: 256 thread
 constexpr int kRowsPerWg = 8;  // batch rows per workgroup
 constexpr int kMaxJ = 8;
 
+// Four consecutive elements of either type as f32. A load is `*reinterpret_cast<const Quad<T>*>(p)` used as a float4: for float
+// that IS the expression these kernels always had (one 16-byte load; the f32 instances compile to the machine code they had
+// before the element type became a parameter), for __bf16 one 8-byte load whose conversion widens (exact). A store is st4: a
+// plain 16-byte store, or four casts (round to nearest even, NaN kept: psf_common.h `narrow`) and one 8-byte store.
+using Bf16x4 = __bf16 __attribute__((ext_vector_type(4)));
+struct Bf16Quad {
+  Bf16x4 v;
+  __device__ __forceinline__ operator float4() const { return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]); }
+};
+template <typename T>
+struct QuadOf {
+  using type = float4;
+};
+template <>
+struct QuadOf<__bf16> {
+  using type = Bf16Quad;
+};
+template <typename T>
+using Quad = typename QuadOf<T>::type;
+
+template <typename T>
+__device__ __forceinline__ void st4(T* p, const float4& v) {
+  if constexpr (sizeof(T) == 4) {
+    *reinterpret_cast<float4*>(p) = v;
+  } else {
+    Bf16x4 r;
+    r[0] = (__bf16)v.x, r[1] = (__bf16)v.y, r[2] = (__bf16)v.z, r[3] = (__bf16)v.w;
+    *reinterpret_cast<Bf16x4*>(p) = r;
+  }
+}
+
 // U float4 of K per thread: 4 (the first form) or 1 — with 4096-float chunks Temporal Order's head (K = 131072, B = 40) is 160
 // workgroups on 256 CUs and read its 21 MB at 1 TB/s; the launcher takes U = 1 whenever U = 4 would give fewer than 1024.
-template <int J, int U>
+template <typename T, int J, int U>
 __global__ void __launch_bounds__(256)
-flat_head_partial_k(const float* __restrict__ X, const float* __restrict__ W, int32_t B, int64_t K, float* __restrict__ part) {
+flat_head_partial_k(const T* __restrict__ X, const T* __restrict__ W, int32_t B, int64_t K, float* __restrict__ part) {
   __shared__ float red[4][J];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t k0 = (int64_t)blockIdx.x * (1024 * U);
@@ -34,7 +72,7 @@ flat_head_partial_k(const float* __restrict__ X, const float* __restrict__ W, in
     const int64_t k = k0 + 4 * (tid + 256 * u);
 #pragma unroll
     for (int j = 0; j < J; ++j)
-      w[j][u] = k < K ? *reinterpret_cast<const float4*>(W + (int64_t)j * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+      w[j][u] = k < K ? *reinterpret_cast<const Quad<T>*>(W + (int64_t)j * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   const int b0 = blockIdx.y * kRowsPerWg;
   for (int r = 0; r < kRowsPerWg; ++r) {
@@ -44,7 +82,7 @@ flat_head_partial_k(const float* __restrict__ X, const float* __restrict__ W, in
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t k = k0 + 4 * (tid + 256 * u);
-      x[u] = k < K ? *reinterpret_cast<const float4*>(X + (int64_t)b * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+      x[u] = k < K ? *reinterpret_cast<const Quad<T>*>(X + (int64_t)b * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     float s[J];
 #pragma unroll
@@ -73,24 +111,37 @@ flat_head_partial_k(const float* __restrict__ X, const float* __restrict__ W, in
 
 // out[i] = bias + sum over the chunks of part[c][i]: one wave per output; lane l adds chunks l, l + 64, ... in ascending order,
 // then the 64 lane sums are combined by a fixed butterfly (one thread per output walking all chunks took 32 us for the 128
-// chunks of the genome head).
+// chunks of the genome head). T = __bf16: the bias is widened, added in f32, and the total rounded once at the store.
+template <typename T>
 __global__ void __launch_bounds__(64)
-flat_head_reduce_k(const float* __restrict__ part, const float* __restrict__ bias, int32_t chunks, int32_t n, int32_t J,
-                   float* __restrict__ out) {
+flat_head_reduce_k(const float* __restrict__ part, const T* __restrict__ bias, int32_t chunks, int32_t n, int32_t J,
+                   T* __restrict__ out) {
   const int i = blockIdx.x;  // i = b * J + j
   const int lane = threadIdx.x;
   float s = 0.f;
   for (int c = lane; c < chunks; c += 64) s += part[(int64_t)c * n + i];
 #pragma unroll
   for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);
-  if (lane == 0) out[i] = s + (bias ? bias[i % J] : 0.f);
+  if (lane == 0) out[i] = (T)(s + (bias ? (float)bias[i % J] : 0.f));
 }
 
 template <int J>
 void launch_partial(const float* X, const float* W, int32_t B, int64_t K, float* part, int chunks, int u, hipStream_t s) {
   const dim3 grid(chunks, (B + kRowsPerWg - 1) / kRowsPerWg);
-  if (u == 4) hipLaunchKernelGGL((flat_head_partial_k<J, 4>), grid, dim3(256), 0, s, X, W, B, K, part);
-  else hipLaunchKernelGGL((flat_head_partial_k<J, 1>), grid, dim3(256), 0, s, X, W, B, K, part);
+  if (u == 4) hipLaunchKernelGGL((flat_head_partial_k<float, J, 4>), grid, dim3(256), 0, s, X, W, B, K, part);
+  else hipLaunchKernelGGL((flat_head_partial_k<float, J, 1>), grid, dim3(256), 0, s, X, W, B, K, part);
+}
+template <int J>
+void launch_partial(const __bf16* X, const __bf16* W, int32_t B, int64_t K, float* part, int chunks, int u, hipStream_t s) {
+  const dim3 grid(chunks, (B + kRowsPerWg - 1) / kRowsPerWg);
+  if (u == 4) hipLaunchKernelGGL((flat_head_partial_k<__bf16, J, 4>), grid, dim3(256), 0, s, X, W, B, K, part);
+  else hipLaunchKernelGGL((flat_head_partial_k<__bf16, J, 1>), grid, dim3(256), 0, s, X, W, B, K, part);
+}
+void launch_reduce(const float* part, const float* bias, int chunks, int n, int32_t J, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(flat_head_reduce_k<float>, dim3(n), dim3(64), 0, s, part, bias, chunks, n, J, out);
+}
+void launch_reduce(const float* part, const __bf16* bias, int chunks, int n, int32_t J, __bf16* out, hipStream_t s) {
+  hipLaunchKernelGGL(flat_head_reduce_k<__bf16>, dim3(n), dim3(64), 0, s, part, bias, chunks, n, J, out);
 }
 
 // chunk size of a launch: 4096 floats, or 1024 when that would leave fewer than 1024 workgroups
@@ -112,19 +163,19 @@ constexpr int kBwdMaxJ = 16;  // (the forward kernel keeps J weight chunks in re
 constexpr int kBwdThreads = 64;  // one wave per workgroup: K / 256 workgroups (512 at K = 131072) keep every CU busy
 constexpr int kBwdRows = 8;      // batch rows whose loads are issued together (the sums still run in ascending row order)
 
-template <int J, bool DX, bool DW>
+template <typename T, int J, bool DX, bool DW>
 __global__ void __launch_bounds__(kBwdThreads)
-flat_head_bwd_k(const float* __restrict__ dY, const float* __restrict__ X, const float* __restrict__ W, float* __restrict__ dX,
-                float* __restrict__ dW, int32_t B, int64_t K) {
-  extern __shared__ float sdy[];  // [B][J]
-  for (int i = threadIdx.x; i < B * J; i += kBwdThreads) sdy[i] = dY[i];
+flat_head_bwd_k(const T* __restrict__ dY, const T* __restrict__ X, const T* __restrict__ W, T* __restrict__ dX, T* __restrict__ dW,
+                int32_t B, int64_t K) {
+  extern __shared__ float sdy[];  // [B][J], f32 for either element type
+  for (int i = threadIdx.x; i < B * J; i += kBwdThreads) sdy[i] = (float)dY[i];
   __syncthreads();
   const int64_t k = 4 * ((int64_t)blockIdx.x * kBwdThreads + threadIdx.x);
   if (k >= K) return;
   float4 w[J], acc[J];
 #pragma unroll
   for (int j = 0; j < J; ++j) {
-    if (DX) w[j] = *reinterpret_cast<const float4*>(W + (int64_t)j * K + k);
+    if (DX) w[j] = *reinterpret_cast<const Quad<T>*>(W + (int64_t)j * K + k);
     acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   for (int b0 = 0; b0 < B; b0 += kBwdRows) {
@@ -133,7 +184,7 @@ flat_head_bwd_k(const float* __restrict__ dY, const float* __restrict__ X, const
 #pragma unroll
       for (int u = 0; u < kBwdRows; ++u) {
         const int b = b0 + u < B ? b0 + u : B - 1;  // clamped: a finished row is read again, not used
-        x[u] = *reinterpret_cast<const float4*>(X + (int64_t)b * K + k);
+        x[u] = *reinterpret_cast<const Quad<T>*>(X + (int64_t)b * K + k);
       }
     }
 #pragma unroll
@@ -159,37 +210,54 @@ flat_head_bwd_k(const float* __restrict__ dY, const float* __restrict__ X, const
             d.z = fmaf(g[j], w[j].z, d.z);
             d.w = fmaf(g[j], w[j].w, d.w);
           }
-          *reinterpret_cast<float4*>(dX + (int64_t)b * K + k) = d;
+          st4(dX + (int64_t)b * K + k, d);
         }
       }
     }
   }
   if (DW) {
 #pragma unroll
-    for (int j = 0; j < J; ++j) *reinterpret_cast<float4*>(dW + (int64_t)j * K + k) = acc[j];
+    for (int j = 0; j < J; ++j) st4(dW + (int64_t)j * K + k, acc[j]);
   }
+}
+
+template <int J>
+void launch_bwd(const __bf16* dY, const __bf16* X, const __bf16* W, __bf16* dX, __bf16* dW, int32_t B, int64_t K, hipStream_t s) {
+  const unsigned blocks = (unsigned)((K / 4 + kBwdThreads - 1) / kBwdThreads);
+  const size_t lds = (size_t)B * J * sizeof(float);
+  if (dX && dW) hipLaunchKernelGGL((flat_head_bwd_k<__bf16, J, true, true>), dim3(blocks), dim3(kBwdThreads), lds, s, dY, X, W, dX, dW, B, K);
+  else if (dX) hipLaunchKernelGGL((flat_head_bwd_k<__bf16, J, true, false>), dim3(blocks), dim3(kBwdThreads), lds, s, dY, X, W, dX, dW, B, K);
+  else hipLaunchKernelGGL((flat_head_bwd_k<__bf16, J, false, true>), dim3(blocks), dim3(kBwdThreads), lds, s, dY, X, W, dX, dW, B, K);
 }
 
 template <int J>
 void launch_bwd(const float* dY, const float* X, const float* W, float* dX, float* dW, int32_t B, int64_t K, hipStream_t s) {
   const unsigned blocks = (unsigned)((K / 4 + kBwdThreads - 1) / kBwdThreads);
   const size_t lds = (size_t)B * J * sizeof(float);
-  if (dX && dW) hipLaunchKernelGGL((flat_head_bwd_k<J, true, true>), dim3(blocks), dim3(kBwdThreads), lds, s, dY, X, W, dX, dW, B, K);
-  else if (dX) hipLaunchKernelGGL((flat_head_bwd_k<J, true, false>), dim3(blocks), dim3(kBwdThreads), lds, s, dY, X, W, dX, dW, B, K);
-  else hipLaunchKernelGGL((flat_head_bwd_k<J, false, true>), dim3(blocks), dim3(kBwdThreads), lds, s, dY, X, W, dX, dW, B, K);
+  if (dX && dW) hipLaunchKernelGGL((flat_head_bwd_k<float, J, true, true>), dim3(blocks), dim3(kBwdThreads), lds, s, dY, X, W, dX, dW, B, K);
+  else if (dX) hipLaunchKernelGGL((flat_head_bwd_k<float, J, true, false>), dim3(blocks), dim3(kBwdThreads), lds, s, dY, X, W, dX, dW, B, K);
+  else hipLaunchKernelGGL((flat_head_bwd_k<float, J, false, true>), dim3(blocks), dim3(kBwdThreads), lds, s, dY, X, W, dX, dW, B, K);
 }
 
-}  // namespace
-
-extern "C" int psf_flat_head_bwd_f32(const float* dY, const float* X, const float* W, float* dX, float* dW, int32_t B,
-                                     int64_t K, int32_t J, void* stream) {
-  if (!dY || (!dX && !dW)) return psf_internal_fail(PSF_E_NULL, "psf_flat_head_bwd: dY and at least one of dX, dW must be non-NULL");
-  if ((dW && !X) || (dX && !W)) return psf_internal_fail(PSF_E_NULL, "psf_flat_head_bwd: dW needs X, dX needs W");
+// The host side of both backward entries: everything is validated before the first HIP call. A thread's four elements are 16
+// bytes of f32 or 8 bytes of bf16, which is the alignment asked for; the f32 entry's messages are what they always were.
+template <typename T>
+int head_bwd(const T* dY, const T* X, const T* W, T* dX, T* dW, int32_t B, int64_t K, int32_t J, void* stream) {
+  constexpr bool kBf = sizeof(T) == 2;
+  if (!dY || (!dX && !dW))
+    return psf_internal_fail(PSF_E_NULL, kBf ? "psf_flat_head_bwd_bf16: dY and at least one of dX, dW must be non-NULL"
+                                             : "psf_flat_head_bwd: dY and at least one of dX, dW must be non-NULL");
+  if ((dW && !X) || (dX && !W))
+    return psf_internal_fail(PSF_E_NULL, kBf ? "psf_flat_head_bwd_bf16: dW needs X, dX needs W" : "psf_flat_head_bwd: dW needs X, dX needs W");
   if (B < 1 || B > kBwdMaxB || K < 4 || (K & 3) || J < 1 || J > kBwdMaxJ || K / 4 / kBwdThreads > 0x7ffffffe)
-    return psf_internal_fail(PSF_E_SHAPE, "psf_flat_head_bwd: need 1 <= B <= 1024, K a positive multiple of 4, 1 <= J <= 16");
+    return psf_internal_fail(PSF_E_SHAPE, kBf ? "psf_flat_head_bwd_bf16: need 1 <= B <= 1024, K a positive multiple of 4, 1 <= J <= 16"
+                                              : "psf_flat_head_bwd: need 1 <= B <= 1024, K a positive multiple of 4, 1 <= J <= 16");
   const uintptr_t al = (dW ? reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(dW) : 0) |
                        (dX ? reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(dX) : 0);
-  if (al & 15) return psf_internal_fail(PSF_E_ALIGN, "psf_flat_head_bwd: X, W, dX and dW must be 16-byte aligned");
+  if (al & (4 * sizeof(T) - 1))
+    return psf_internal_fail(PSF_E_ALIGN, kBf ? "psf_flat_head_bwd_bf16: X, W, dX and dW must be 8-byte aligned"
+                                              : "psf_flat_head_bwd: X, W, dX and dW must be 16-byte aligned");
+  if (kBf && (reinterpret_cast<uintptr_t>(dY) & 1)) return psf_internal_fail(PSF_E_ALIGN, "psf_flat_head_bwd_bf16: dY must be 2-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   switch (J) {
     case 1: launch_bwd<1>(dY, X, W, dX, dW, B, K, s); break;
@@ -213,22 +281,50 @@ extern "C" int psf_flat_head_bwd_f32(const float* dY, const float* X, const floa
   return e == hipSuccess ? PSF_OK : psf_internal_fail((int)e, hipGetErrorString(e));
 }
 
+}  // namespace
+
+extern "C" int psf_flat_head_bwd_f32(const float* dY, const float* X, const float* W, float* dX, float* dW, int32_t B,
+                                     int64_t K, int32_t J, void* stream) {
+  return head_bwd<float>(dY, X, W, dX, dW, B, K, J, stream);
+}
+
+extern "C" int psf_flat_head_bwd_bf16(const uint16_t* dY, const uint16_t* X, const uint16_t* W, uint16_t* dX, uint16_t* dW, int32_t B,
+                                      int64_t K, int32_t J, void* stream) {
+  return head_bwd<__bf16>(reinterpret_cast<const __bf16*>(dY), reinterpret_cast<const __bf16*>(X), reinterpret_cast<const __bf16*>(W),
+                          reinterpret_cast<__bf16*>(dX), reinterpret_cast<__bf16*>(dW), B, K, J, stream);
+}
+
 extern "C" int64_t psf_flat_head_workspace(int32_t B, int64_t K, int32_t J) {
   if (B < 1 || K < 4 || (K & 3) || J < 1 || J > kMaxJ) return -1;
   return ((K + 1023) / 1024) * (int64_t)B * J * (int64_t)sizeof(float);  // sized for the smaller chunk
 }
 
-extern "C" int psf_flat_head_f32(const float* X, const float* W, const float* bias, float* out, int32_t B, int64_t K,
-                                 int32_t J, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!X || !W || !out || !workspace) return psf_internal_fail(PSF_E_NULL, "psf_flat_head: X, W, out and workspace must be non-NULL");
+namespace {
+
+// The host side of both forward entries; the workspace holds the f32 partial sums for either element type.
+template <typename T>
+int head_fwd(const T* X, const T* W, const T* bias, T* out, int32_t B, int64_t K, int32_t J, void* workspace, int64_t workspace_bytes,
+             void* stream) {
+  constexpr bool kBf = sizeof(T) == 2;
+  if (!X || !W || !out || !workspace)
+    return psf_internal_fail(PSF_E_NULL, kBf ? "psf_flat_head_bf16: X, W, out and workspace must be non-NULL"
+                                             : "psf_flat_head: X, W, out and workspace must be non-NULL");
   const int64_t need = psf_flat_head_workspace(B, K, J);
-  if (need < 0) return psf_internal_fail(PSF_E_SHAPE, "psf_flat_head: need B >= 1, K a positive multiple of 4, 1 <= J <= 8");
-  if (workspace_bytes < need) return psf_internal_fail(PSF_E_SHAPE, "psf_flat_head: workspace smaller than psf_flat_head_workspace(B, K, J)");
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
-    return psf_internal_fail(PSF_E_ALIGN, "psf_flat_head: X and W must be 16-byte aligned");
+  if (need < 0)
+    return psf_internal_fail(PSF_E_SHAPE, kBf ? "psf_flat_head_bf16: need B >= 1, K a positive multiple of 4, 1 <= J <= 8"
+                                              : "psf_flat_head: need B >= 1, K a positive multiple of 4, 1 <= J <= 8");
+  if (workspace_bytes < need)
+    return psf_internal_fail(PSF_E_SHAPE, kBf ? "psf_flat_head_bf16: workspace smaller than psf_flat_head_workspace(B, K, J)"
+                                              : "psf_flat_head: workspace smaller than psf_flat_head_workspace(B, K, J)");
+  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W)) & (4 * sizeof(T) - 1))
+    return psf_internal_fail(PSF_E_ALIGN, kBf ? "psf_flat_head_bf16: X and W must be 8-byte aligned" : "psf_flat_head: X and W must be 16-byte aligned");
+  if (kBf && (((bias ? reinterpret_cast<uintptr_t>(bias) : 0) | reinterpret_cast<uintptr_t>(out)) & 1))
+    return psf_internal_fail(PSF_E_ALIGN, "psf_flat_head_bf16: bias and out must be 2-byte aligned");
+  if (kBf && (reinterpret_cast<uintptr_t>(workspace) & 3))
+    return psf_internal_fail(PSF_E_ALIGN, "psf_flat_head_bf16: workspace must be 4-byte aligned");
   const int u = head_unroll(B, K);
   const int64_t chunks64 = (K + 1024 * u - 1) / (1024 * u);
-  if (chunks64 > 0x7fffffff) return psf_internal_fail(PSF_E_SHAPE, "psf_flat_head: K too large");
+  if (chunks64 > 0x7fffffff) return psf_internal_fail(PSF_E_SHAPE, kBf ? "psf_flat_head_bf16: K too large" : "psf_flat_head: K too large");
   const int chunks = (int)chunks64;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   float* part = reinterpret_cast<float*>(workspace);
@@ -242,8 +338,20 @@ extern "C" int psf_flat_head_f32(const float* X, const float* W, const float* bi
     case 7: launch_partial<7>(X, W, B, K, part, chunks, u, s); break;
     default: launch_partial<8>(X, W, B, K, part, chunks, u, s); break;
   }
-  const int n = B * J;
-  hipLaunchKernelGGL(flat_head_reduce_k, dim3(n), dim3(64), 0, s, part, bias, chunks, n, J, out);
+  launch_reduce(part, bias, chunks, B * J, J, out, s);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? PSF_OK : psf_internal_fail((int)e, hipGetErrorString(e));
+}
+
+}  // namespace
+
+extern "C" int psf_flat_head_f32(const float* X, const float* W, const float* bias, float* out, int32_t B, int64_t K,
+                                 int32_t J, void* workspace, int64_t workspace_bytes, void* stream) {
+  return head_fwd<float>(X, W, bias, out, B, K, J, workspace, workspace_bytes, stream);
+}
+
+extern "C" int psf_flat_head_bf16(const uint16_t* X, const uint16_t* W, const uint16_t* bias, uint16_t* out, int32_t B, int64_t K,
+                                  int32_t J, void* workspace, int64_t workspace_bytes, void* stream) {
+  return head_fwd<__bf16>(reinterpret_cast<const __bf16*>(X), reinterpret_cast<const __bf16*>(W), reinterpret_cast<const __bf16*>(bias),
+                          reinterpret_cast<__bf16*>(out), B, K, J, workspace, workspace_bytes, stream);
 }

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import dp, synth_data
+from . import dp, psfnet, synth_data, token_linear
 from .synthetic_psf import PSFNet
 from .train import DeviceBatches, GraphedStep, TrainModel, count_params, make_adam, seed_everything, train_epoch
 
@@ -147,25 +147,40 @@ def main(argv=None):
     ap.add_argument("--graph", action="store_true",
                     help="capture the training step in a HIP graph and replay it (train.GraphedStep; with several ranks the "
                          "gradient all-reduce and the optimizer step stay outside the graph)")
+    ap.add_argument("--bf16", action="store_true",
+                    help="train the network in bfloat16 on the library's bf16 routes (token embedding, FLATTEN head) with f32 "
+                         "master weights in Adam; --problem order on one rank only")
     ap.add_argument("--force-allreduce", action="store_true",
                     help="run the flat gradient all-reduce even in a 1-rank group (RCCL path check on a 1-GPU box)")
     args = ap.parse_args(argv)
 
+    if args.bf16 and args.problem != "order":
+        raise SystemExit("--bf16 needs --problem order: the real-valued input layer of the adding problem has no bf16 route")
     rank, world, device = dp.init_from_env()
     if device.type != "cuda":
         raise SystemExit("training needs an MI355X: the chord-spmm path has no CPU implementation")
+    if args.bf16 and world > 1:
+        raise SystemExit("--bf16 runs on one rank: dp.FlatGradAllReduce takes float32 gradients")
     cfg_training = config[args.problem]["training"]
     batch = args.batch_size or cfg_training["batch_size"]
     epochs = args.epochs if args.epochs is not None else cfg_training["num_train_steps"]
 
     seed_everything(42)
     net = build_model(args.problem, args.n_vec).to(device)
+    if args.bf16:
+        # the bf16 token model on the library: embedding + table gradient and the FLATTEN head on their bf16 instances (both
+        # opt-in routes), Adam on f32 master weights below. fused_mlp.bf16_train_route and chord.bf16_chain_bwd_route stay at
+        # their defaults: separately gated opt-ins.
+        net = net.to(torch.bfloat16)
+        token_linear.bf16_route = "always"
+        psfnet.bf16_head_route = "always"
     dp.broadcast_parameters(net)
     if rank == 0:
         print('Number of trainable parameters', count_params(net))
     # --graph: one process captures the whole step (optimizer included: capturable Adam); under data parallelism the
     # graph holds forward + backward and the all-reduce + optimizer step stay eager (train.GraphedStep)
-    optimizer = make_adam(net.parameters(), cfg_training["learning_rate"], capturable=args.graph and world == 1)
+    optimizer = make_adam(net.parameters(), cfg_training["learning_rate"], capturable=args.graph and world == 1,
+                          master_weights=args.bf16)
     loss = nn.MSELoss() if args.problem == "adding" else nn.CrossEntropyLoss()
     force = args.force_allreduce and torch.distributed.is_initialized()
     reducer = dp.FlatGradAllReduce(net.parameters(), force=force) if (world > 1 or force) else None
@@ -192,13 +207,14 @@ def main(argv=None):
                               "n_gpus": world, "batch_per_gpu": batch, "steps": stats["steps"],
                               "ms_per_step": dt * 1e3 / max(stats["steps"], 1),
                               "value": world * batch * args.n_vec * stats["steps"] / dt, "unit": "tokens/s",
-                              "loss": stats["loss"], "hip_graph": bool(args.graph)}))
-        return {"net": net, "reducer": reducer, "stats": stats}
+                              "loss": stats["loss"], "hip_graph": bool(args.graph),
+                              "dtype": "bf16" if args.bf16 else "f32"}))
+        return {"net": net, "reducer": reducer, "stats": stats, "optimizer": optimizer}
 
     history = TrainModel(net=net, trainloader=trainloader, valloader=valloader, testloader=testloader, n_epochs=epochs,
                test_freq=cfg_training["eval_frequency"], optimizer=optimizer, loss=loss, problem=args.problem,
                saving_criteria=99.5, reducer=reducer, is_main=rank == 0, graphed=graphed)
-    return {"net": net, "reducer": reducer, "history": history}
+    return {"net": net, "reducer": reducer, "history": history, "optimizer": optimizer}
 
 
 if __name__ == "__main__":

@@ -117,13 +117,91 @@ class _FlatHeadFn(torch.autograd.Function):
         return d_flat, d_w, d_b
 
 
+# "never" (default) or "always": whether a bf16 FLATTEN head runs on the library's bf16 instances of the streaming kernels
+# (psf_flat_head_bf16, psf_flat_head_bwd_bf16: f32 arithmetic in the f32 kernels' order, one rounding per result element) instead
+# of the stock nn.Linear. Opt-in like token_linear.bf16_route: the logits and gradients then come from another summation order
+# than the library GEMM's (same single rounding; profiles/bf16_flat_head_ab.md). At "never" nothing below is reached.
+bf16_head_route = "never"
+
+
+def _bf16_head_wanted() -> bool:
+    if bf16_head_route not in ("never", "always"):
+        raise ValueError(f"psfnet.bf16_head_route must be 'never' or 'always', not {bf16_head_route!r}")
+    return bf16_head_route == "always"
+
+
+class _FlatHeadBf16Fn(torch.autograd.Function):
+    """``_FlatHeadFn`` on bf16 operands: ``psf_flat_head_bf16`` and ``psf_flat_head_bwd_bf16`` (csrc/flat_head.hip; 8-byte vectors).
+    The same split: J <= 8 the kernel forward, 9 <= J <= 16 ``F.linear`` forward and the kernel backward; B > 1024 or a gradient
+    that is not bf16 takes the two ``mm`` calls."""
+
+    @staticmethod
+    def forward(ctx, flat, weight, bias):
+        lib = _lib.load()
+        flat_c, w_c = flat.contiguous(), weight.contiguous()
+        B, K = flat_c.shape
+        J = w_c.shape[0]
+        ctx.save_for_backward(flat_c, w_c)
+        ctx.has_bias = bias is not None
+        if J > 8:
+            return torch.nn.functional.linear(flat_c, w_c, bias)
+        ws_bytes = lib.psf_flat_head_workspace(B, K, J)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=flat.device)  # f32 partial sums for either element type
+        out = torch.empty((B, J), dtype=torch.bfloat16, device=flat.device)
+        with torch.cuda.device(flat.device):
+            rc = lib.psf_flat_head_bf16(flat_c.data_ptr(), w_c.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                        out.data_ptr(), B, K, J, ws.data_ptr(), ws_bytes, _lib.stream_ptr(flat.device))
+        _lib.check(rc, "psf_flat_head_bf16")
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        flat, weight = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        d_flat = d_w = None
+        B, K = flat.shape
+        J = weight.shape[0]
+        if (need_x or need_w) and dy.dtype == torch.bfloat16 and B <= 1024 and flat.data_ptr() % 8 == 0 and weight.data_ptr() % 8 == 0:
+            dy_c = dy.contiguous()
+            d_flat = torch.empty_like(flat) if need_x else None
+            d_w = torch.empty_like(weight) if need_w else None
+            with torch.cuda.device(flat.device):
+                rc = _lib.load().psf_flat_head_bwd_bf16(dy_c.data_ptr(), flat.data_ptr(), weight.data_ptr(),
+                                                        d_flat.data_ptr() if need_x else None, d_w.data_ptr() if need_w else None,
+                                                        B, K, J, _lib.stream_ptr(flat.device))
+            _lib.check(rc, "psf_flat_head_bwd_bf16")
+        else:
+            d_flat = dy.mm(weight.to(dy.dtype)) if need_x else None
+            d_w = dy.t().mm(flat.to(dy.dtype)).to(weight.dtype) if need_w else None
+            if d_flat is not None:
+                d_flat = d_flat.to(flat.dtype)
+        d_b = dy.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return d_flat, d_w, d_b
+
+
+def _bf16_head_applies(final: nn.Module, flat: torch.Tensor) -> bool:
+    """The gate of the bf16 route: everything bf16, on the GPU, contiguous and 8-byte aligned, outside autocast."""
+    bf16 = torch.bfloat16
+    w, b = final.weight, final.bias
+    return (final.out_features <= 16 and flat.is_cuda and flat.dim() == 2 and flat.dtype == bf16 and w.dtype == bf16 and w.is_cuda
+            and (b is None or (b.dtype == bf16 and b.is_cuda and b.is_contiguous()))
+            # K >= 4096 is the f32 route's measured gate, carried over to bf16 unmeasured
+            and flat.shape[1] % 4 == 0 and flat.shape[1] >= 4096
+            # psf_flat_head_bf16 reads 8-byte vectors and returns PSF_E_ALIGN otherwise: such a view takes the stock module
+            and flat.is_contiguous() and flat.data_ptr() % 8 == 0 and w.is_contiguous() and w.data_ptr() % 8 == 0
+            and not autocast_on(flat))
+
+
 def _flat_head(final: nn.Module, flat: torch.Tensor) -> torch.Tensor:
     """``final(flat)`` for the FLATTEN head, Linear(N*C -> n_class) on [B, N*C] (psf.py:129-134). As a GEMM the
     library takes 0.57 ms (Adding, one output) or 117 us (Temporal Order, four) at N*C = 131072, B = 64
-    (profiles/r01_e2e_forward_split.log); ``psf_flat_head_f32`` reads the activations once."""
+    (profiles/r01_e2e_forward_split.log); ``psf_flat_head_f32`` reads the activations once. A bf16 head is ``final(flat)``
+    unless ``bf16_head_route`` is "always" (``_FlatHeadBf16Fn``)."""
     if isinstance(final, nn.Sequential) and len(final) > 0 and isinstance(final[0], nn.Linear):
         # the non-linear head (LRA/psf.py: Linear(N*C -> hidden), GELU, Linear(hidden -> n_class)): its first layer is the wide one
         return final[1:](_flat_head(final[0], flat))
+    if _bf16_head_wanted() and isinstance(final, nn.Linear) and _bf16_head_applies(final, flat):
+        return _FlatHeadBf16Fn.apply(flat, final.weight, final.bias)
     if (isinstance(final, nn.Linear) and final.out_features <= 16 and flat.is_cuda and flat.dim() == 2
             and flat.dtype == torch.float32 and final.weight.dtype == torch.float32 and flat.shape[1] % 4 == 0
             and flat.shape[1] >= 4096
