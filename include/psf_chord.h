@@ -307,6 +307,25 @@ int psf_linear_wgrad_f32(const float* X, const float* dY, int64_t T, int32_t m, 
  * e.g. one MLP's hidden block inside the stacked hidden layer of all MLPs. */
 int psf_linear_wgrad_strided_f32(const float* X, int64_t ldx, const float* dY, int64_t ldy, int64_t T, int32_t m, int32_t n,
                                  float* dWt, float* db, void* workspace, int64_t workspace_bytes, void* stream);
+/*
+ * The same gradients for a layer whose operands are bf16 (raw bits), on the bf16 matrix core (csrc/linear_wgrad_bf16.hip):
+ *     dWt[j*m + i] = rne_bf16(sum_t dY[t*ldy + j] * X[t*ldx + i])     db[j] = rne_bf16(sum_t dY[t*ldy + j])   (db may be NULL)
+ *   T >= 1, 1 <= m, n <= 128, ldx >= m, ldy >= n (row strides in elements: column slices of wider arrays are taken as they
+ *   are). Arithmetic contract: the operands are bf16; every product is exact in f32; all accumulation is in f32; each output
+ *   element is rounded to bf16 ONCE, to nearest even, at the store; there are no float atomics and the partial sums are
+ *   combined in a fixed order, so two calls on the same operands give the same bits, eagerly and from a replayed graph. The
+ *   summation order is this kernel's own (16 tokens per matrix instruction, one slab of rows per wave, slabs combined in a
+ *   fixed tree): it is NOT the order of psf_linear_wgrad_f32, and the two entries' f32 sums may differ in their last bits.
+ *   No load leaves [X, X + (T-1) ldx + m) or [dY, dY + (T-1) ldy + n).
+ *   Alignment: with g(ld) the largest power of two <= 8 that divides ld (the elements one vector load takes), X must be
+ *   aligned to 2 g(ldx) bytes and dY to 2 g(ldy) bytes — 16 bytes for a row stride that is a multiple of 8, 2 bytes for an odd
+ *   one; dWt and db to 2 bytes, workspace to 4: PSF_E_ALIGN otherwise, before any launch. NULL X, dY, dWt or workspace:
+ *   PSF_E_NULL; sizes or strides out of range, or fewer than psf_linear_wgrad_bf16_workspace(T, m, n) workspace bytes (-1
+ *   for unsupported sizes): PSF_E_SHAPE — the f32 entry's codes.
+ */
+int64_t psf_linear_wgrad_bf16_workspace(int64_t T, int32_t m, int32_t n);
+int psf_linear_wgrad_bf16(const uint16_t* X, int64_t ldx, const uint16_t* dY, int64_t ldy, int64_t T, int32_t m, int32_t n,
+                          uint16_t* dWt, uint16_t* db, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * out[i] = ((srcs[0][i] + srcs[1][i]) + srcs[2][i]) + ...   i < n, in that order (separately rounded additions).
@@ -379,6 +398,14 @@ int psf_embed_tokens_bf16(const int64_t* idx, const uint16_t* table, const uint1
  */
 int psf_affine_rows_f32(const float* x, const float* W, const float* bias, float* out, int64_t T, int32_t K, int32_t E,
                         void* stream);
+/*
+ * The same rows on bf16 (raw bits): x [T,K], W [E,K], bias [E] or NULL, out [T,E] bf16, 1 <= K <= 3, E a multiple of 8 in
+ * 8..1024 (PSF_E_SHAPE), out 16-byte aligned, x, W and bias 2-byte aligned (PSF_E_ALIGN). Per element: the f32 chain
+ * x_0 w_e0, fused adds of x_1 w_e1 and x_2 w_e2 (the products of bf16 values are exact in f32), the bias added in f32, and one
+ * rounding to bf16, to nearest even.
+ */
+int psf_affine_rows_bf16(const uint16_t* x, const uint16_t* W, const uint16_t* bias, uint16_t* out, int64_t T, int32_t K,
+                         int32_t E, void* stream);
 /*
  * Its gradient with respect to the table:  dTable[v,:] = sum over {t : idx[t] == v} of dOut[t,:]   (fully written;
  * the caller zeroes a padding row). No sort, no atomics, no host read-back: deterministic (a fixed order of

@@ -74,6 +74,8 @@ SIGNATURES = {
     "psf_linear_wgrad_workspace": ([c_i64, c_i32, c_i32], c_i64),
     "psf_linear_wgrad_f32": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),
     "psf_linear_wgrad_strided_f32": ([c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),
+    "psf_linear_wgrad_bf16_workspace": ([c_i64, c_i32, c_i32], c_i64),
+    "psf_linear_wgrad_bf16": ([c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, _DA, c_i64, c_vp], ctypes.c_int),  # (f32 workspace)
     "psf_adam_step_f32": ([ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), _I64P, c_i32,
                            ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp, c_vp], ctypes.c_int),
     # f32 master weights for bf16 parameters: (master, params_bf16, grads_bf16, exp_avg, exp_avg_sq) pointer tables
@@ -84,6 +86,7 @@ SIGNATURES = {
     "psf_embed_tokens_f32": ([c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp], ctypes.c_int),
     "psf_embed_tokens_bf16": ([_DA, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp], ctypes.c_int),  # (idx is int64)
     "psf_affine_rows_f32": ([c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp], ctypes.c_int),
+    "psf_affine_rows_bf16": ([c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp], ctypes.c_int),
     "psf_embed_tokens_bwd_workspace": ([c_i64, c_i32, c_i32], c_i64),
     "psf_embed_tokens_bwd_f32": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),
     "psf_embed_tokens_bwd_bf16": ([_DA, c_vp, c_i64, c_i32, c_i32, c_vp, _DA, c_i64, c_vp], ctypes.c_int),  # (idx int64, f32 workspace)

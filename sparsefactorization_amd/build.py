@@ -28,7 +28,7 @@ WIN_TGS = list(range(7))
 HEADERS = ["psf_common.h", "fwd_kernels.h", "fwd_window.h", "fwd_window_launch.h", "bwd_kernels.h",
            "bwd_window.h", "bwd_dw_chunk.h", "bwd_window_launch.h", "bwd_fused.h", "bwd_fused_bf16.h", "fwd_chain_lds.h", "fwd_chain_lds_bf16.h", "fwd_chain_lds_launch.h", "bwd_chain_lds.h", "bwd_chain_lds_bf16.h", "fwd_mlp_step.h", "fwd_mlp_step_launch.h", "mixer_lds.h", "mixer_lds_launch.h", "mixer_lds_bf16.h", "mixer_lds_bf16_launch.h", "mlp_x3_image.h", "mlp_bf16_image.h", "mlp_bf16_tile.h", "mlp_fwd_x3.h", "mlp_x3_common.h", "mlp_planes.h", "x3_gemm.h",
            os.path.join("..", "..", "include", "psf_chord.h"), os.path.join("..", "..", "include", "psf_chord_tuning.h")]
-SOURCES = ["psf_chord.hip", "fwd_window_inst.hip", "bwd_window_inst.hip", "bwd_fused_bf16_inst.hip", "linear_wgrad.hip",
+SOURCES = ["psf_chord.hip", "fwd_window_inst.hip", "bwd_window_inst.hip", "bwd_fused_bf16_inst.hip", "linear_wgrad.hip", "linear_wgrad_bf16.hip",
            "fwd_chain_lds_inst.hip", "fwd_chain_lds_bf16_inst.hip", "bwd_chain_lds_inst.hip", "bwd_chain_lds_bf16_inst.hip", "fwd_mlp_step_inst.hip", "mixer_lds_inst.hip", "mixer_lds_bf16_inst.hip", "embed.hip", "flat_head.hip", "sum_tensors.hip", "adam.hip", "mlp_fwd.hip", "mlp_fwd_x3.hip", "mlp_fwd_bf16.hip", "mlp_bwd.hip", "mlp_bwd_bf16.hip", "mlp_wide.hip", "stream_mix.hip"]
 
 # -ffp-contract=off: products and sums stay separate roundings (bitwise parity with the CPU oracle).
@@ -76,6 +76,9 @@ def _unit_table():
     reported as warnings in their failing form, and errors only in R3_STRICT_UNITS: isa_lint.py's docstring)."""
     units = [(os.path.join(OBJ_DIR, "psf_chord.o"), os.path.join(CSRC, "psf_chord.hip"), []),
              (os.path.join(OBJ_DIR, "linear_wgrad.o"), os.path.join(CSRC, "linear_wgrad.hip"), []),
+             # the bf16 weight gradient: a unit of its own (linear_wgrad's ISA is what it was). NO_SCRATCH_UNITS: the 4 x 4-tile
+             # instance holds 256 accumulator registers and must not spill
+             (os.path.join(OBJ_DIR, "linear_wgrad_bf16.o"), os.path.join(CSRC, "linear_wgrad_bf16.hip"), []),
              # -fno-slp-vectorize: the LDS-resident chain's multiply-add loop is faster on scalar f32 instructions than on the
              # v_pk_* pairs hipcc builds from it (Pathfinder chain 41.4 -> 33.9 us, profiles/r04p_lib_ab_noslp.log; the
              # per-step window kernels are the other way round: 367 -> 386 us at cfg2)
@@ -147,7 +150,7 @@ def check_no_scratch(unit_name: str, asm_path: str) -> dict:
 R3_STRICT_UNITS = ("fwd_mlp_step", "mixer_lds")
 LINT_LOG = os.path.join(OBJ_DIR, "isa_lint.log")  # one line per unit: functions, errors, notes, R3-pattern sites
 # units none of whose kernels may use scratch memory (a spill): checked in the code-object metadata of the kept assembly
-NO_SCRATCH_UNITS = ("mlp_bwd_bf16", "bwd_chain_lds_bf16")
+NO_SCRATCH_UNITS = ("mlp_bwd_bf16", "bwd_chain_lds_bf16", "linear_wgrad_bf16")
 
 
 def kernel_resources(asm_path: str) -> dict:
@@ -170,7 +173,7 @@ def kernel_resources(asm_path: str) -> dict:
 def _unit_weight(unit) -> int:
     """Rough compile cost of a unit (seconds on this container), for the order in which the pool starts them."""
     name = os.path.basename(unit[0])
-    for prefix, w in (("fwd_mlp_step", 30), ("mlp_bwd_bf16", 12), ("mlp_bwd", 28), ("fwd_chain_lds", 26), ("bwd_chain_lds", 20), ("mlp_wide", 24), ("fwd_window", 16),
+    for prefix, w in (("fwd_mlp_step", 30), ("mlp_bwd_bf16", 12), ("mlp_bwd", 28), ("linear_wgrad_bf16", 20), ("fwd_chain_lds", 26), ("bwd_chain_lds", 20), ("mlp_wide", 24), ("fwd_window", 16),
                       ("bwd_window_mid", 14), ("bwd_window", 12), ("bwd_fused_bf16", 10), ("mixer_lds", 10), ("mlp_fwd", 8), ("psf_chord", 8)):
         if name.startswith(prefix):
             return w

@@ -154,6 +154,52 @@ extern "C" int psf_affine_rows_f32(const float* x, const float* W, const float* 
   return e == hipSuccess ? PSF_OK : psf_internal_fail((int)e, hipGetErrorString(e));
 }
 
+// bf16 x, W, bias and out: a thread keeps EIGHT features (one 16-byte vector of the output). The same f32 chain on the widened
+// operands (the products of bf16 values are exact in f32), the bias added in f32, one rounding to bf16 at the store.
+namespace {
+
+__global__ void __launch_bounds__(256)
+affine_rows_bf16_k(const __bf16* __restrict__ x, const __bf16* __restrict__ W, const __bf16* __restrict__ bias, __bf16* __restrict__ out,
+                   int64_t T, int32_t K, int32_t E8) {
+  const int per = 256 / E8;  // positions per workgroup per pass (E8 <= 128: host-checked)
+  const int tid = threadIdx.x, e8 = tid % E8, tl = tid / E8;
+  if (tl >= per) return;
+  float w0[8], w1[8], w2[8], bb[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const __bf16* w = W + (int64_t)(8 * e8 + j) * K;
+    w0[j] = (float)w[0], w1[j] = K > 1 ? (float)w[1] : 0.f, w2[j] = K > 2 ? (float)w[2] : 0.f;
+    bb[j] = bias ? (float)bias[8 * e8 + j] : 0.f;
+  }
+  for (int64_t t = (int64_t)blockIdx.x * per + tl; t < T; t += (int64_t)gridDim.x * per) {
+    const float x0 = (float)x[t * K], x1 = K > 1 ? (float)x[t * K + 1] : 0.f, x2 = K > 2 ? (float)x[t * K + 2] : 0.f;
+    Bf16x8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = (__bf16)__fadd_rn(fmaf(x2, w2[j], fmaf(x1, w1[j], __fmul_rn(x0, w0[j]))), bb[j]);
+    reinterpret_cast<Bf16x8*>(out)[t * E8 + e8] = r;
+  }
+}
+
+}  // namespace
+
+extern "C" int psf_affine_rows_bf16(const uint16_t* x, const uint16_t* W, const uint16_t* bias, uint16_t* out, int64_t T, int32_t K,
+                                    int32_t E, void* stream) {
+  if (!x || !W || !out) return psf_internal_fail(PSF_E_NULL, "psf_affine_rows_bf16: x, W and out must be non-NULL");
+  if (T < 0 || K < 1 || K > 3 || E < 8 || (E & 7) || E > 1024)
+    return psf_internal_fail(PSF_E_SHAPE, "psf_affine_rows_bf16: need T >= 0, 1 <= K <= 3, E a multiple of 8 in 8..1024");
+  if ((reinterpret_cast<uintptr_t>(out) & 15) || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(bias)) & 1))
+    return psf_internal_fail(PSF_E_ALIGN, "psf_affine_rows_bf16: out must be 16-byte aligned, x, W and bias 2-byte aligned");
+  if (T == 0) return PSF_OK;
+  const int per = 256 / (E / 8);
+  const int64_t blocks = (T + per - 1) / per;
+  const int grid = (int)(blocks < 8192 ? blocks : 8192);
+  hipLaunchKernelGGL(affine_rows_bf16_k, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const __bf16*>(x), reinterpret_cast<const __bf16*>(W), reinterpret_cast<const __bf16*>(bias),
+                     reinterpret_cast<__bf16*>(out), T, K, E / 8);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PSF_OK : psf_internal_fail((int)e, hipGetErrorString(e));
+}
+
 // ------------------------------------------------------------------------------------------------------
 // Gradient of the table:  dTable[v, :] = sum over the tokens t with idx[t] == v of dOut[t, :]
 // ------------------------------------------------------------------------------------------------------

@@ -150,12 +150,18 @@ def main(argv=None):
     ap.add_argument("--bf16", action="store_true",
                     help="train the network in bfloat16 on the library's bf16 routes (token embedding, FLATTEN head) with f32 "
                          "master weights in Adam; --problem order on one rank only")
+    ap.add_argument("--bf16-linear", action="store_true",
+                    help="with --bf16: the token-wise Linear layers on the library's bf16 weight-gradient and input-row kernels "
+                         "(token_linear.bf16_linear_route); what lets --problem adding train in bfloat16")
     ap.add_argument("--force-allreduce", action="store_true",
                     help="run the flat gradient all-reduce even in a 1-rank group (RCCL path check on a 1-GPU box)")
     args = ap.parse_args(argv)
 
-    if args.bf16 and args.problem != "order":
-        raise SystemExit("--bf16 needs --problem order: the real-valued input layer of the adding problem has no bf16 route")
+    if args.bf16_linear and not args.bf16:
+        raise SystemExit("--bf16-linear needs --bf16: it routes the Linear layers of a bfloat16 network")
+    if args.bf16 and args.problem != "order" and not args.bf16_linear:
+        raise SystemExit("--bf16 needs --problem order: the real-valued input layer of the adding problem has no bf16 route "
+                         "without --bf16-linear")
     rank, world, device = dp.init_from_env()
     if device.type != "cuda":
         raise SystemExit("training needs an MI355X: the chord-spmm path has no CPU implementation")
@@ -174,6 +180,8 @@ def main(argv=None):
         net = net.to(torch.bfloat16)
         token_linear.bf16_route = "always"
         psfnet.bf16_head_route = "always"
+        if args.bf16_linear:  # TokenLinear weight gradients and init_linear's rows on their bf16 instances (a third opt-in)
+            token_linear.bf16_linear_route = "always"
     dp.broadcast_parameters(net)
     if rank == 0:
         print('Number of trainable parameters', count_params(net))
@@ -182,6 +190,9 @@ def main(argv=None):
     optimizer = make_adam(net.parameters(), cfg_training["learning_rate"], capturable=args.graph and world == 1,
                           master_weights=args.bf16)
     loss = nn.MSELoss() if args.problem == "adding" else nn.CrossEntropyLoss()
+    if args.bf16 and args.problem == "adding":
+        mse = loss
+        loss = lambda pred, target: mse(pred.float(), target)  # noqa: E731  (a bf16 prediction's squared error, taken in f32)
     force = args.force_allreduce and torch.distributed.is_initialized()
     reducer = dp.FlatGradAllReduce(net.parameters(), force=force) if (world > 1 or force) else None
 
@@ -190,6 +201,8 @@ def main(argv=None):
     Xtr, Ytr = make_split(args.problem, hi - lo, args.n_vec, device, 1000 + rank)
     Xva, Yva = make_split(args.problem, args.eval_seqs, args.n_vec, device, 2000)
     Xte, Yte = make_split(args.problem, args.eval_seqs, args.n_vec, device, 3000)
+    if args.bf16 and Xtr.is_floating_point():  # the real-valued inputs of the adding problem feed a bf16 init_linear
+        Xtr, Xva, Xte = (X.to(torch.bfloat16) for X in (Xtr, Xva, Xte))
     mk = lambda X, Y, shuffle: DeviceBatches(X, Y, batch, shuffle=shuffle, drop_last=True)  # noqa: E731
     trainloader, valloader, testloader = mk(Xtr, Ytr, True), mk(Xva, Yva, False), mk(Xte, Yte, False)
 

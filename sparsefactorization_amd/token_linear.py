@@ -6,7 +6,8 @@ gradients differ: for T = B*N tokens and layer widths of 2..128 they are a reduc
 of a few hundred numbers, for which library GEMMs take ~1 ms per layer (84 % of a training step at
 Order/Adding N = 16384 — profiles/r01_train_step_profile.log). ``psf_linear_wgrad_f32`` (csrc/linear_wgrad.hip)
 streams X and dY once through the f32 matrix core instead. Layers outside its range (wide ListOps layers,
-fp64, CPU tensors) use the stock autograd formulas.
+fp64, CPU tensors) use the stock autograd formulas. bf16 layers do too, unless ``bf16_linear_route`` is "always":
+then ``psf_linear_wgrad_bf16`` (csrc/linear_wgrad_bf16.hip) takes them on the bf16 matrix core.
 """
 from __future__ import annotations
 
@@ -30,22 +31,80 @@ def autocast_on(t: torch.Tensor) -> bool:
     return kind in ("cuda", "cpu") and torch.is_autocast_enabled(kind)
 
 
+# "never" (default) or "always": whether the token-wise Linear layers of a bf16 model run on the library's bf16 instances — the
+# weight / bias gradient on psf_linear_wgrad_bf16 (csrc/linear_wgrad_bf16.hip: bf16 matrix core, f32 sums, one rounding) and the
+# rows of a 1-3-input layer on psf_affine_rows_bf16 — instead of the stock F.linear and its library GEMMs. A switch of its own,
+# not a wider meaning of ``bf16_route``: models that run with that one at "always" keep their bits. Opt-in because the weight
+# gradient then comes from another summation order than the library GEMM's (profiles/bf16_linear_wgrad_ab.md). At "never"
+# nothing of it is reached.
+bf16_linear_route = "never"
+
+
+def _bf16_linear_on() -> bool:
+    if bf16_linear_route not in ("never", "always"):
+        raise ValueError(f'token_linear.bf16_linear_route must be "never" or "always", not {bf16_linear_route!r}')
+    return bf16_linear_route == "always"
+
+
 def wgrad_supported(x2d: torch.Tensor, out_features: int) -> bool:
-    return (x2d.is_cuda and x2d.dtype == torch.float32 and x2d.shape[0] >= MIN_TOKENS
-            and x2d.shape[1] <= MAX_WIDTH and out_features <= MAX_WIDTH and not autocast_on(x2d))
+    if x2d.dtype == torch.bfloat16:
+        if not _bf16_linear_on():  # (asked first: a misspelt switch raises for every bf16 layer, wherever its operands live)
+            return False
+    elif x2d.dtype != torch.float32:
+        return False
+    return (x2d.is_cuda and x2d.shape[0] >= MIN_TOKENS and x2d.shape[1] <= MAX_WIDTH and out_features <= MAX_WIDTH
+            and not autocast_on(x2d))
+
+
+def _wgrad_bf16_operand(t: torch.Tensor, width: int) -> torch.Tensor:
+    """``t`` as psf_linear_wgrad_bf16 takes it: unit inner stride, a row stride >= the width, and a base aligned to the vector
+    the entry loads for that row stride (2 g bytes, g the largest power of two <= 8 dividing the stride). A slice that misses
+    any of it is made contiguous (a fresh allocation is aligned for every stride)."""
+    if t.stride(1) != 1 or t.stride(0) < width:
+        return t.contiguous()
+    ld = t.stride(0)
+    if t.data_ptr() % (2 * (8 if ld % 8 == 0 else ld & -ld)):
+        return t.contiguous()
+    return t
+
+
+def _linear_wgrad_bf16(x2d: torch.Tensor, dy2d: torch.Tensor, need_bias: bool):
+    T, m = x2d.shape
+    n = dy2d.shape[1]
+    lib = _lib.load()
+    ws_bytes = lib.psf_linear_wgrad_bf16_workspace(T, m, n)
+    if ws_bytes < 0:
+        raise ValueError(f"psf_linear_wgrad_bf16 does not support T={T}, m={m}, n={n}")
+    x2d, dy2d = _wgrad_bf16_operand(x2d, m), _wgrad_bf16_operand(dy2d, n)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x2d.device)
+    dW = torch.empty((n, m), dtype=torch.bfloat16, device=x2d.device)
+    db = torch.empty(n, dtype=torch.bfloat16, device=x2d.device) if need_bias else None
+    with torch.cuda.device(x2d.device):
+        rc = lib.psf_linear_wgrad_bf16(x2d.data_ptr(), x2d.stride(0), dy2d.data_ptr(), dy2d.stride(0), T, m, n, dW.data_ptr(),
+                                       db.data_ptr() if db is not None else None, ws.data_ptr(), ws_bytes,
+                                       _lib.stream_ptr(x2d.device))
+    _lib.check(rc, "psf_linear_wgrad_bf16")
+    return dW, db
 
 
 def linear_wgrad(x2d: torch.Tensor, dy2d: torch.Tensor, need_bias: bool = True):
-    """(dWeight [n, m], dBias [n] or None) for X [T, m], dY [T, n] on the HIP kernel. Both float32 on one HIP device:
-    anything else is a TypeError (the entry takes raw addresses and would read another dtype's bytes as floats)."""
+    """(dWeight [n, m], dBias [n] or None) for X [T, m], dY [T, n] on the HIP kernel. Both float32 on one HIP device — or, with
+    ``bf16_linear_route`` at "always", both bfloat16: anything else is a TypeError (the entry takes raw addresses and would read
+    another dtype's bytes as its own)."""
     operands = (("x", x2d), ("dy", dy2d))
+    want = torch.float32
+    if isinstance(x2d, torch.Tensor) and x2d.dtype == torch.bfloat16 and _bf16_linear_on():
+        want = torch.bfloat16
+    takes = "float32" if want == torch.float32 else "bfloat16"
     for name, t in operands:  # the element type first, of both operands: the message names the one that is wrong and why
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError(f"linear_wgrad takes float32 tensors on one HIP device; {name} is {getattr(t, 'dtype', type(t))}")
+        if not isinstance(t, torch.Tensor) or t.dtype != want:
+            raise TypeError(f"linear_wgrad takes {takes} tensors on one HIP device; {name} is {getattr(t, 'dtype', type(t))}")
     for name, t in operands:
         if not t.is_cuda or t.device != x2d.device:
-            raise TypeError(f"linear_wgrad takes float32 tensors on one HIP device; {name} is on '{t.device}'"
+            raise TypeError(f"linear_wgrad takes {takes} tensors on one HIP device; {name} is on '{t.device}'"
                             + (f", x on '{x2d.device}'" if t.is_cuda else ""))
+    if want == torch.bfloat16:
+        return _linear_wgrad_bf16(x2d, dy2d, need_bias)
     T, m = x2d.shape
     n = dy2d.shape[1]
     lib = _lib.load()
@@ -68,10 +127,19 @@ def linear_wgrad(x2d: torch.Tensor, dy2d: torch.Tensor, need_bias: bool = True):
     return dW, db
 
 
+def _affine_rows_bf16_supported(x: torch.Tensor, weight: torch.Tensor, bias) -> bool:
+    return (_bf16_linear_on() and x.is_cuda and weight.dtype == torch.bfloat16 and x.dim() >= 2 and 1 <= x.shape[-1] <= 3
+            and weight.dim() == 2 and weight.shape[1] == x.shape[-1] and weight.shape[0] % 8 == 0 and 8 <= weight.shape[0] <= 1024
+            and (bias is None or bias.dtype == torch.bfloat16) and not autocast_on(x))
+
+
 def affine_rows_supported(x: torch.Tensor, weight: torch.Tensor, bias) -> bool:
     """``x @ weight.T + bias`` with at most three inputs per position on the GPU in fp32: psf_affine_rows_f32 (csrc/embed.hip)
     writes the rows in one pass (init_linear of the synthetic PSFNet, SyntheticExperiments/psf.py:153-154: a library GEMM
-    takes 80 us for that K = 2 product at 1 M positions, the pass 25)."""
+    takes 80 us for that K = 2 product at 1 M positions, the pass 25). The bf16 case (psf_affine_rows_bf16, E a multiple of 8)
+    when ``bf16_linear_route`` is "always"."""
+    if x.dtype == torch.bfloat16:
+        return _affine_rows_bf16_supported(x, weight, bias)
     return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() >= 2 and 1 <= x.shape[-1] <= 3
             and weight.dim() == 2 and weight.shape[1] == x.shape[-1] and weight.shape[0] % 4 == 0 and 4 <= weight.shape[0] <= 1024
             and (bias is None or bias.dtype == torch.float32))
@@ -79,16 +147,19 @@ def affine_rows_supported(x: torch.Tensor, weight: torch.Tensor, bias) -> bool:
 
 def affine_rows(x: torch.Tensor, weight: torch.Tensor, bias) -> torch.Tensor:
     """The rows themselves (no autograd). Products summed in input order with fused adds, then one rounded add of the bias —
-    the arithmetic of the mixer kernels' affine recipe, bit for bit."""
+    the arithmetic of the mixer kernels' affine recipe, bit for bit. bf16 operands: the same f32 chain, rounded to bf16 once."""
     K, E = x.shape[-1], weight.shape[0]
     x2 = x.detach().reshape(-1, K).contiguous()
     w = weight.detach().contiguous()
     b = bias.detach().contiguous() if bias is not None else None
-    out = torch.empty((x2.shape[0], E), dtype=torch.float32, device=x.device)
+    out = torch.empty((x2.shape[0], E), dtype=x.dtype, device=x.device)
+    lib = _lib.load()
+    entry, name = ((lib.psf_affine_rows_bf16, "psf_affine_rows_bf16") if x.dtype == torch.bfloat16
+                   else (lib.psf_affine_rows_f32, "psf_affine_rows_f32"))
     with torch.cuda.device(x.device):
-        rc = _lib.load().psf_affine_rows_f32(x2.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, out.data_ptr(),
-                                             x2.shape[0], K, E, _lib.stream_ptr(x.device))
-    _lib.check(rc, "psf_affine_rows_f32")
+        rc = entry(x2.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, out.data_ptr(),
+                   x2.shape[0], K, E, _lib.stream_ptr(x.device))
+    _lib.check(rc, name)
     return out.reshape(*x.shape[:-1], E)
 
 
