@@ -286,6 +286,38 @@ int psf_chord_chain_bwd_lds_bf16(const uint16_t* dOut, const uint16_t* const* W_
                                  const int64_t* offsets, void* stream);
 
 /*
+ * The TRANSPOSED chain: selected rows of the attention map A_b = W_{M-1} ... W_0 (W_final of the LRA/attention_maps scripts) without the
+ * dense [B,N,N] map.
+ *     Y_M = Q;   Y_m = W_m^T (.) Y_{m+1}   for m = M-1 .. 0;   out = Y_0
+ *     Y_m[b,q,c] = sum_k W_m[b,(q-off_k) mod N,k] * Y_{m+1}[b,(q-off_k) mod N,c]
+ * A column c of Q that is one-hot at row r comes back as out[b,:,c] = A_b[r,:]. (A COLUMN of A_b is the forward chain on a
+ * one-hot V0: psf_chord_chain_fwd_*.) Each step is the dV half of psf_chord_spmm_bwd_* (spmul/spmul_cuda.cu:75-84).
+ *   W_steps    host table of M device pointers, W_steps[m] -> W_m [B,N,L]; f32 4-byte, bf16 2-byte aligned
+ *   Q, out, scratch  [B,N,R], 16-byte aligned, pairwise distinct; R a multiple of 4 (f32) or 8 (bf16). Q is never written.
+ *   offsets    as everywhere: NULL = the chord pattern; explicit and negative offsets are reduced mod N
+ * Routes. psf_chord_chain_tr_supported(N, L, R, M, elem_bytes) answers 1 where the entry runs ONE launch
+ * (chord_chain_tr_lds_k, csrc/chain_tr_lds.h): 1 <= N <= 1024, 2 <= L <= 20, 1 <= M <= 64, R as above, elem_bytes 4 or 2. One
+ * thread owns a row, Y and W_m stay in LDS, a workgroup holds up to four 16-byte column groups and a sequence with more
+ * columns spreads over ceil(R / 16) (f32; bf16: ceil(R / 32)) workgroups; `scratch` is not touched and may be NULL. (The
+ * query has no B: a batch whose B * workgroups per sequence exceeds the grid limit of 2^31 - 1 takes the per-step route too.) Elsewhere
+ * (0) the library issues the M per-step dV launches of psf_chord_spmm_bwd_* itself, taking turns between `scratch` and `out`
+ * so that the last one writes `out`; `scratch` may be NULL for M = 1, otherwise a NULL `scratch` returns PSF_E_UNSUPPORTED (not
+ * an error, as a NULL dX_steps of psf_chord_chain_bwd_f32). No knob selects between the two.
+ * Arithmetic, on either route: the bits of M calls of psf_chord_spmm_bwd_{f32,bf16} with dW = NULL, W_{M-1} first, each
+ * result fed to the next. f32: links ascending from +0, product and sum rounded separately (the CPU oracle's dV). bf16: f32
+ * accumulator, one fused multiply-add per link, one rounding to bf16 per step; the rounded value enters the next step.
+ * Validation, before any launch: M < 1, a bad B / N / L / R (PSF_E_SHAPE); NULL W_steps, Q or out (PSF_E_NULL); the NULL
+ * scratch above (PSF_E_UNSUPPORTED); B == 0 returns PSF_OK; then a NULL W_steps[m] (PSF_E_NULL), Q, out, scratch not
+ * distinct (PSF_E_ALIAS), alignment (PSF_E_ALIGN). No allocation, no synchronisation: the entries can be captured in a HIP
+ * graph ("Streams" above). Added without a version change.
+ */
+int psf_chord_chain_tr_supported(int64_t N, int32_t L, int64_t R, int32_t M, int32_t elem_bytes);
+int psf_chord_chain_tr_f32(const float* const* W_steps, const float* Q, float* out, float* scratch, int32_t M,
+                           int64_t B, int64_t N, int32_t L, int64_t R, const int64_t* offsets, void* stream);
+int psf_chord_chain_tr_bf16(const uint16_t* const* W_steps, const uint16_t* Q, uint16_t* out, uint16_t* scratch, int32_t M,
+                            int64_t B, int64_t N, int32_t L, int64_t R, const int64_t* offsets, void* stream);
+
+/*
  * (Rounds 2-4 also exported training variants that kept a link-major side copy of W's far columns for the dV kernel —
  * "..._chain_fwd_far_f32", "..._spmm_bwd_far_f32", "..._bwd_far_first_link". A wash end to end
  * (profiles/r02n_far_copy.log, r03aj_farcopy_in_step_ab.log), off by default since round 2, removed in round 5.)

@@ -8,11 +8,13 @@ Python surface. Importing the package does not need a GPU; calling an operator d
 library — nothing falls back to the CPU.
 """
 from ._lib import PSFLibraryError, build_info, describe_fwd, get_tuning, set_tuning, tuning
+from .attention_map import attention_cols, attention_rows, chain_transposed
 from .chord import chord_chain, chord_spmm, get_chord_indices_assym, offsets_from_index, spmm
 from .spmul import SparseMultiply, get_offsets
 
 __all__ = [
     "spmm", "chord_spmm", "chord_chain", "get_chord_indices_assym", "offsets_from_index",
+    "chain_transposed", "attention_rows", "attention_cols",
     "SparseMultiply", "get_offsets", "PSFLibraryError", "build_info", "describe_fwd", "set_tuning", "get_tuning", "tuning",
 ]
 __version__ = "0.1.0"

@@ -71,6 +71,10 @@ SIGNATURES = {
     "psf_chord_chain_bwd_lds_bf16_supported": ([c_i64, c_i32, c_i64, c_i32], ctypes.c_int),
     "psf_chord_chain_bwd_lds_bf16": ([c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i32, c_i32,
                                       c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
+    # the transposed chain (rows of the attention map): (W_steps, Q, out, scratch, M, B, N, L, R, offsets, stream)
+    "psf_chord_chain_tr_supported": ([c_i64, c_i32, c_i64, c_i32, c_i32], ctypes.c_int),
+    "psf_chord_chain_tr_f32": ([ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
+    "psf_chord_chain_tr_bf16": ([ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
     "psf_linear_wgrad_workspace": ([c_i64, c_i32, c_i32], c_i64),
     "psf_linear_wgrad_f32": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),
     "psf_linear_wgrad_strided_f32": ([c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], ctypes.c_int),

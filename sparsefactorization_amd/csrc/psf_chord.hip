@@ -20,6 +20,7 @@
 #include "bwd_window_launch.h"
 #include "bwd_chain_lds.h"
 #include "bwd_chain_lds_bf16.h"
+#include "chain_tr_lds.h"
 #include "fwd_chain_lds_bf16.h"
 #include "fwd_chain_lds_launch.h"
 #include "fwd_kernels.h"
@@ -898,6 +899,48 @@ int chain_bwd_impl(const K* dOut, const K* const* W_steps, const K* V0, const K*
   return PSF_OK;
 }
 
+// The transposed chain Y_m = W_m^T (.) Y_{m+1}, m = M-1 .. 0 (K = float or __bf16): rows of the attention map. One launch
+// where chain_tr_lds.h covers the shape; otherwise the M per-step dV launches of psf_chord_spmm_bwd_* (dW = NULL), taking
+// turns between `scratch` and `out` so that step 0 writes `out`. Same bits either way.
+template <typename K>
+int chain_tr_impl(const K* const* W_steps, const K* Q, K* out, K* scratch, int32_t M, int64_t B, int64_t N, int32_t L, int64_t R,
+                  const int64_t* offsets, void* stream) {
+  constexpr int VECW = 16 / (int)sizeof(K);
+  if (M < 1) return fail(PSF_E_SHAPE, "M must be >= 1");
+  if (!W_steps || !Q || !out) return fail(PSF_E_NULL, "a required pointer is NULL");
+  if (int rc = check_dims(B, N, L, R, N * R)) return rc;
+  if (R % VECW != 0) return fail(PSF_E_SHAPE, "R=%lld must be a multiple of %d", (long long)R, VECW);
+  const bool one_launch = chain_tr_lds_fits(N, L, R, M, (int)sizeof(K)) && B * ((R / VECW + kChainTrGroups - 1) / kChainTrGroups) <= 0x7fffffff;
+  if (!one_launch && M > 1 && !scratch) return PSF_E_UNSUPPORTED;  // (the per-step route needs the second buffer)
+  if (B == 0) return PSF_OK;
+  for (int m = 0; m < M; ++m)
+    if (!W_steps[m]) return fail(PSF_E_NULL, "step %d: NULL pointer", m);
+  if (out == Q || (scratch && (scratch == Q || scratch == out))) return fail(PSF_E_ALIAS, "Q, out and scratch must be distinct");
+  for (int m = 0; m < M; ++m)
+    if (!aligned_to(W_steps[m], sizeof(K))) return fail(PSF_E_ALIGN, "step %d: W must be %d-byte aligned", m, (int)sizeof(K));
+  if (!aligned_to(Q, 16) || !aligned_to(out, 16) || (scratch && !aligned_to(scratch, 16)))
+    return fail(PSF_E_ALIGN, "Q, out and scratch must be 16-byte aligned");
+  if (one_launch) {
+    ChainTrArgs<K> a;
+    for (int m = 0; m < kChainMaxSteps; ++m) a.W[m] = m < M ? W_steps[m] : nullptr;
+    a.Q = Q, a.out = out, a.M = M, a.N = (int32_t)N, a.R = (int32_t)R;
+    a.CG = (int32_t)(R / VECW), a.chunks = (a.CG + kChainTrGroups - 1) / kChainTrGroups;
+    Offsets offs;
+    make_offsets(N, L, offsets, &offs);
+    hipError_t e = launch_chain_tr_lds(L, a, offs, B, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, kIsBf16<K> ? "chord_chain_tr_lds<bf16> launch" : "chord_chain_tr_lds launch");
+    return PSF_OK;
+  }
+  const Tuning tn = snapshot();
+  const K* y = Q;
+  for (int m = M - 1; m >= 0; --m) {
+    K* dst = (m & 1) ? scratch : out;  // step 0 writes out
+    if (int rc = bwd_impl<K>(tn, y, W_steps[m], nullptr, nullptr, dst, B, N, L, R, N * R, offsets, stream)) return rc;
+    y = dst;
+  }
+  return PSF_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // the mixer with W computed inside the step (fwd_mlp_step.h)
 // ------------------------------------------------------------------------------------------------------
@@ -1307,6 +1350,21 @@ int psf_chord_chain_bwd_lds_bf16(const uint16_t* dOut, const uint16_t* const* W_
   hipError_t e = launch_chain_bwd_lds_bf16(L, (int)(C / 8), use_residual != 0, a, offs, (int)B, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail_hip(e, "chord_chain_bwd_lds<bf16> launch");
   return PSF_OK;
+}
+
+int psf_chord_chain_tr_supported(int64_t N, int32_t L, int64_t R, int32_t M, int32_t elem_bytes) {
+  return chain_tr_lds_fits(N, L, R, M, elem_bytes) ? 1 : 0;
+}
+
+int psf_chord_chain_tr_f32(const float* const* W_steps, const float* Q, float* out, float* scratch, int32_t M, int64_t B,
+                           int64_t N, int32_t L, int64_t R, const int64_t* offsets, void* stream) {
+  return chain_tr_impl<float>(W_steps, Q, out, scratch, M, B, N, L, R, offsets, stream);
+}
+
+int psf_chord_chain_tr_bf16(const uint16_t* const* W_steps, const uint16_t* Q, uint16_t* out, uint16_t* scratch, int32_t M,
+                            int64_t B, int64_t N, int32_t L, int64_t R, const int64_t* offsets, void* stream) {
+  return chain_tr_impl<__bf16>(reinterpret_cast<const __bf16* const*>(W_steps), reinterpret_cast<const __bf16*>(Q),
+                               reinterpret_cast<__bf16*>(out), reinterpret_cast<__bf16*>(scratch), M, B, N, L, R, offsets, stream);
 }
 
 int64_t psf_mixer_fwd_workspace(int64_t N, int32_t E, int32_t M, const int32_t* h, int64_t C, int32_t L) {

@@ -31,6 +31,7 @@ import torch
 from torch import nn
 
 from . import _lib, fused_mixer, fused_mlp
+from .attention_map import attention_cols, attention_rows
 from .chord import chord_chain, chord_spmm, get_chord_indices_assym
 from .token_linear import TokenEmbedding, TokenLinear, autocast_on, embed_tokens
 
@@ -544,6 +545,15 @@ class ChangedPSF(LRAPSFNet):
             eye = torch.eye(n, n, dtype=V.dtype, device=V.device)
             W_final = chord_chain(Ws, eye, False)
         return self.pool_and_classify(V), W_final
+
+    def attention(self, data, rows=None, cols=None):
+        """``(logits, A[:, rows, :] or None, A[:, :, cols] or None)`` without the dense map: what the two scripts read of it
+        (psf_utils_attn_IMDb.py:67: row 0; pathfinder_inference.py:319-321: 18 columns). ``rows`` / ``cols``: [R] or [B, R] indices.
+        The logits are ``forward(data)[0]``'s; the rows [B, R, N] and columns [B, N, R] are detached (attention_map.py)."""
+        Ws: List[torch.Tensor] = []
+        V = self.features(data, Ws)
+        return (self.pool_and_classify(V), None if rows is None else attention_rows(Ws, rows),
+                None if cols is None else attention_cols(Ws, cols))
 
 
 class GraphedInference:
