@@ -64,7 +64,8 @@ extern "C" {
 #endif
 
 #define PSF_ABI_VERSION 2 /* 2 (round 5): the three "far" training entries are gone, psf_device_info is new, per-step mixer kernels take rows only.
-                             The bf16 entry points (..._bf16) were added later without a version change: the change is additive. */
+                             The bf16 entry points (..._bf16) were added later without a version change: the change is additive.
+                             So were psf_chord_chain_last_f32, psf_chord_chain_last_supported and psf_describe_chain_last. */
 
 #define PSF_MAX_LINKS 64 /* L <= 64: N = 2^63 would need 64 links */
 
@@ -224,6 +225,29 @@ int psf_chord_chain_fwd_bf16(const uint16_t* const* W_steps, const uint16_t* V0,
                              int32_t M, int32_t use_residual,
                              int64_t B, int64_t N, int32_t L, int64_t C, int64_t v0_batch_stride,
                              const int64_t* offsets, void* stream);
+
+/*
+ * The same chain when only its LAST result is wanted, for long f32 sequences, in exactly ONE launch: out [B,N,C] receives
+ * X_M and no other X_m reaches memory (csrc/fwd_chain_regs.h: a workgroup owns one sequence and one channel pair, X lives in
+ * registers, W is streamed through LDS). The bits are those of psf_chord_chain_fwd_f32's out_steps[M-1].
+ *   Covers N = 16384, L = 15, C a multiple of 4, 1 <= M <= 64, the chord offsets (offsets NULL or equal to them), every
+ *   W_steps[m], V0 and out 16-byte aligned, and a V0 that is not broadcast when it is also the residual. Anything else returns
+ *   PSF_E_UNSUPPORTED (not an error, nothing launched): the caller runs psf_chord_chain_fwd_f32. There is no fallback here.
+ *   Errors, before that: M < 1 (PSF_E_SHAPE), a NULL pointer (PSF_E_NULL), the dimensions' limits (PSF_E_SHAPE), out == V0 or
+ *   out == W_steps[m] (PSF_E_ALIAS), a pointer off its element size (PSF_E_ALIGN).
+ * psf_chord_chain_last_supported answers 1 where a caller should PREFER this entry: the shape is covered (w_align: the
+ * alignment in bytes that every W_steps[m], V0 and out is known to have; default_offsets: 1 for the chord pattern) and knob
+ * "chain_fused" is 2, or 1 with a grid that fills its rounds: a workgroup takes a whole CU, so B * C / 2 workgroups run in
+ * ceil(workgroups / CUs) rounds of one workgroup's time, and the one launch wins only where the workgroups are at least
+ * 95 % of rounds * CUs, up to the four rounds measured (csrc/fwd_chain_regs_launch.h: chain_regs_automatic; the CU count is
+ * the current device's, 256 where no device answers). Just above a multiple of the CU count it answers 0. The entry itself
+ * runs wherever it fits.
+ */
+int psf_chord_chain_last_f32(const float* const* W_steps, const float* V0, float* out, int32_t M, int32_t use_residual,
+                             int64_t B, int64_t N, int32_t L, int64_t C, int64_t v0_batch_stride,
+                             const int64_t* offsets, void* stream);
+int psf_chord_chain_last_supported(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, int32_t w_align,
+                                   int32_t use_residual, int64_t v0_batch_stride, int32_t default_offsets);
 
 /*
  * Whole backward chain of the same loop in one call (SyntheticExperiments/psf.py:172-188 differentiated;
@@ -774,6 +798,10 @@ int psf_describe_chain_fwd_dtype(int64_t B, int64_t N, int32_t L, int64_t C, int
  * TR=256 near=10 far=5 fronts=2" for the fused step, "<dW kernel> + <dV kernel>" for the two-kernel routes (window, chunk or
  * generic kernels). elem_bytes: 2 (bf16), 4 (f32) or 8 (f64). Added without a version change. */
 int psf_describe_bwd(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_bytes, char* buf, int32_t cap);
+/* What psf_chord_chain_last_f32 does with a chain of 16-byte aligned operands, a full-batch V0 and the chord offsets:
+ * "chord_chain_regs_k<f32,L=15,T=512,J=32> one launch for all 14 steps, ..., automatic" (or "on request only": the entry runs
+ * it, psf_chord_chain_last_supported answers 0), or "declined (PSF_E_UNSUPPORTED): ..." for a shape it does not cover. */
+int psf_describe_chain_last(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, char* buf, int32_t cap);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,11 @@ SIGNATURES = {
     "psf_chord_spmm_fwd_bf16": (_STEP, ctypes.c_int),
     "psf_chord_spmm_bwd_bf16": (_BWD, ctypes.c_int),
     "psf_chord_chain_fwd_bf16": (_CHAIN, ctypes.c_int),
+    # X_M of a long f32 chain in one launch: (W_steps, V0, out, M, use_residual, B, N, L, C, v0_batch_stride, offsets, stream);
+    # PSF_E_UNSUPPORTED where it does not apply, never a fallback. _supported: (B, N, L, C, M, w_align, use_residual,
+    # v0_batch_stride, default_offsets) -> 1 where the caller should prefer it
+    "psf_chord_chain_last_f32": ([ctypes.POINTER(c_vp), c_vp, c_vp, c_i32, c_i32, c_i64, c_i64, c_i32, c_i64, c_i64, _I64P, c_vp], ctypes.c_int),
+    "psf_chord_chain_last_supported": ([c_i64, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_i64, c_i32], ctypes.c_int),
     "psf_chord_chain_bwd_supported": ([c_i64, c_i32, c_i64, c_i32], ctypes.c_int),
     "psf_chord_chain_bwd_f32": ([c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_i32, c_i32,
                                  c_i64, c_i64, c_i32, c_i64, _I64P, c_vp], ctypes.c_int),
@@ -145,6 +150,7 @@ SIGNATURES = {
     "psf_describe_bwd": ([c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
     "psf_describe_chain_fwd": ([c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
     "psf_describe_chain_fwd_dtype": ([c_i64, c_i64, c_i32, c_i64, c_i32, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
+    "psf_describe_chain_last": ([c_i64, c_i64, c_i32, c_i64, c_i32, ctypes.c_char_p, c_i32], ctypes.c_int),
 }
 
 
@@ -296,6 +302,13 @@ def describe_bwd(B: int, N: int, L: int, C: int, elem_bytes: int = 4) -> str:
 def describe_chain_fwd(B: int, N: int, L: int, C: int, M: int, elem_bytes: int = 4) -> str:
     buf = ctypes.create_string_buffer(256)
     check(load().psf_describe_chain_fwd_dtype(B, N, L, C, M, elem_bytes, buf, 256), "psf_describe_chain_fwd_dtype")
+    return buf.value.decode()
+
+
+def describe_chain_last(B: int, N: int, L: int, C: int, M: int) -> str:
+    """What psf_chord_chain_last_f32 does with this chain (aligned operands, chord offsets, current knobs)."""
+    buf = ctypes.create_string_buffer(256)
+    check(load().psf_describe_chain_last(B, N, L, C, M, buf, 256), "psf_describe_chain_last")
     return buf.value.decode()
 
 

@@ -26,10 +26,10 @@ ARCH = "gfx950"
 WIN_TGS = list(range(7))
 
 HEADERS = ["psf_common.h", "fwd_kernels.h", "fwd_window.h", "fwd_window_launch.h", "bwd_kernels.h",
-           "bwd_window.h", "bwd_dw_chunk.h", "bwd_window_launch.h", "bwd_fused.h", "bwd_fused_bf16.h", "fwd_chain_lds.h", "fwd_chain_lds_bf16.h", "fwd_chain_lds_launch.h", "bwd_chain_lds.h", "bwd_chain_lds_bf16.h", "chain_tr_lds.h", "fwd_mlp_step.h", "fwd_mlp_step_launch.h", "mixer_lds.h", "mixer_lds_launch.h", "mixer_lds_bf16.h", "mixer_lds_bf16_launch.h", "mlp_x3_image.h", "mlp_bf16_image.h", "mlp_bf16_tile.h", "mlp_fwd_x3.h", "mlp_x3_common.h", "mlp_planes.h", "x3_gemm.h",
+           "bwd_window.h", "bwd_dw_chunk.h", "bwd_window_launch.h", "bwd_fused.h", "bwd_fused_bf16.h", "fwd_chain_lds.h", "fwd_chain_lds_bf16.h", "fwd_chain_lds_launch.h", "fwd_chain_regs.h", "fwd_chain_regs_launch.h", "bwd_chain_lds.h", "bwd_chain_lds_bf16.h", "chain_tr_lds.h", "fwd_mlp_step.h", "fwd_mlp_step_launch.h", "mixer_lds.h", "mixer_lds_launch.h", "mixer_lds_bf16.h", "mixer_lds_bf16_launch.h", "mlp_x3_image.h", "mlp_bf16_image.h", "mlp_bf16_tile.h", "mlp_fwd_x3.h", "mlp_x3_common.h", "mlp_planes.h", "x3_gemm.h",
            os.path.join("..", "..", "include", "psf_chord.h"), os.path.join("..", "..", "include", "psf_chord_tuning.h")]
 SOURCES = ["psf_chord.hip", "fwd_window_inst.hip", "bwd_window_inst.hip", "bwd_fused_bf16_inst.hip", "linear_wgrad.hip", "linear_wgrad_bf16.hip",
-           "fwd_chain_lds_inst.hip", "fwd_chain_lds_bf16_inst.hip", "bwd_chain_lds_inst.hip", "bwd_chain_lds_bf16_inst.hip", "chain_tr_lds_inst.hip", "fwd_mlp_step_inst.hip", "mixer_lds_inst.hip", "mixer_lds_bf16_inst.hip", "embed.hip", "flat_head.hip", "sum_tensors.hip", "adam.hip", "mlp_fwd.hip", "mlp_fwd_x3.hip", "mlp_fwd_bf16.hip", "mlp_bwd.hip", "mlp_bwd_bf16.hip", "mlp_wide.hip", "stream_mix.hip"]
+           "fwd_chain_lds_inst.hip", "fwd_chain_lds_bf16_inst.hip", "fwd_chain_regs_inst.hip", "bwd_chain_lds_inst.hip", "bwd_chain_lds_bf16_inst.hip", "chain_tr_lds_inst.hip", "fwd_mlp_step_inst.hip", "mixer_lds_inst.hip", "mixer_lds_bf16_inst.hip", "embed.hip", "flat_head.hip", "sum_tensors.hip", "adam.hip", "mlp_fwd.hip", "mlp_fwd_x3.hip", "mlp_fwd_bf16.hip", "mlp_bwd.hip", "mlp_bwd_bf16.hip", "mlp_wide.hip", "stream_mix.hip"]
 
 # -ffp-contract=off: products and sums stay separate roundings (bitwise parity with the CPU oracle).
 HIPCC_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
@@ -85,6 +85,10 @@ def _unit_table():
              (os.path.join(OBJ_DIR, "fwd_chain_lds.o"), os.path.join(CSRC, "fwd_chain_lds_inst.hip"), ["-fno-slp-vectorize"]),
              # the bf16 forward chain: a unit of its own, so the f32 unit's ISA is what it was; same flag, same reason
              (os.path.join(OBJ_DIR, "fwd_chain_lds_bf16.o"), os.path.join(CSRC, "fwd_chain_lds_bf16_inst.hip"), ["-fno-slp-vectorize"]),
+             # the register-resident last-result chain of long sequences: 192 of its 256 registers hold X_m, X_{m+1} and V0, so
+             # NO_SCRATCH_UNITS (a spill's reload is a vector-memory operation the kernel's counted waits do not expect). The
+             # chains' flag: scalar f32 arithmetic needs 13 registers fewer here than the v_pk_* pairs (241 against 254)
+             (os.path.join(OBJ_DIR, "fwd_chain_regs.o"), os.path.join(CSRC, "fwd_chain_regs_inst.hip"), ["-fno-slp-vectorize"]),
              (os.path.join(OBJ_DIR, "bwd_chain_lds.o"), os.path.join(CSRC, "bwd_chain_lds_inst.hip"), ["-fno-slp-vectorize"]),
              # the bf16 backward chain: a unit of its own (the f32 unit's ISA is what it was), the f32 unit's flag.
              # NO_SCRATCH_UNITS: none of its instances may spill
@@ -154,7 +158,7 @@ def check_no_scratch(unit_name: str, asm_path: str) -> dict:
 R3_STRICT_UNITS = ("fwd_mlp_step", "mixer_lds")
 LINT_LOG = os.path.join(OBJ_DIR, "isa_lint.log")  # one line per unit: functions, errors, notes, R3-pattern sites
 # units none of whose kernels may use scratch memory (a spill): checked in the code-object metadata of the kept assembly
-NO_SCRATCH_UNITS = ("mlp_bwd_bf16", "bwd_chain_lds_bf16", "linear_wgrad_bf16", "chain_tr_lds")
+NO_SCRATCH_UNITS = ("mlp_bwd_bf16", "bwd_chain_lds_bf16", "linear_wgrad_bf16", "chain_tr_lds", "fwd_chain_regs")
 
 
 def kernel_resources(asm_path: str) -> dict:
@@ -177,7 +181,7 @@ def kernel_resources(asm_path: str) -> dict:
 def _unit_weight(unit) -> int:
     """Rough compile cost of a unit (seconds on this container), for the order in which the pool starts them."""
     name = os.path.basename(unit[0])
-    for prefix, w in (("fwd_mlp_step", 30), ("mlp_bwd_bf16", 12), ("mlp_bwd", 28), ("linear_wgrad_bf16", 20), ("fwd_chain_lds", 26), ("bwd_chain_lds", 20), ("chain_tr_lds", 20), ("mlp_wide", 24), ("fwd_window", 16),
+    for prefix, w in (("fwd_mlp_step", 30), ("mlp_bwd_bf16", 12), ("mlp_bwd", 28), ("linear_wgrad_bf16", 20), ("fwd_chain_regs", 4), ("fwd_chain_lds", 26), ("bwd_chain_lds", 20), ("chain_tr_lds", 20), ("mlp_wide", 24), ("fwd_window", 16),
                       ("bwd_window_mid", 14), ("bwd_window", 12), ("bwd_fused_bf16", 10), ("mixer_lds", 10), ("mlp_fwd", 8), ("psf_chord", 8)):
         if name.startswith(prefix):
             return w

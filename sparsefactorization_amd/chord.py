@@ -253,6 +253,11 @@ def _sum_tensors(terms: Sequence[torch.Tensor]) -> torch.Tensor:
     return out
 
 
+#: times psf_chord_chain_last_f32 declined a chain that psf_chord_chain_last_supported had just accepted (the per-step route ran
+#: instead): 0 in normal use; anything else is a quiet fallback worth looking at
+chain_last_declined = 0
+
+
 def _chain_forward_raw(V0, use_residual, offsets, Ws, keep_all):
     """The M launches of the chain (one library call). keep_all: every step's result in its own buffer (they are the saved
     inputs of the backward steps); otherwise two buffers take turns. Returns (V0 contiguous, [W_m contiguous], outs, geometry)."""
@@ -266,11 +271,32 @@ def _chain_forward_raw(V0, use_residual, offsets, Ws, keep_all):
     if use_residual and stride0 == 0 and B != 1:
         raise ValueError("a broadcast V0 cannot be the residual")
     dev = _require_hip(V0c, *Ws)
-    nbuf = M if keep_all else min(M, 2)
-    bufs = [torch.empty((B, N, C), dtype=V0c.dtype, device=dev) for _ in range(nbuf)]
-    outs = [bufs[m % nbuf] for m in range(M)]
     lib = _lib.load()
-    w_tab = (ctypes.c_void_p * M)(*[w.data_ptr() for w in Ws])
+    w_ptrs = [w.data_ptr() for w in Ws]
+    w_tab = (ctypes.c_void_p * M)(*w_ptrs)
+    spare = None  # an output buffer the declined entry below left unused: the per-step route's first
+    if not keep_all and V0c.dtype == torch.float32:
+        # only X_M is wanted: long sequences have a launch of their own for that (psf_chord_chain_last_f32: X in registers, one
+        # output buffer, no X_m in memory). The library says where it is to be preferred. w_align covers the operands that
+        # exist before the question is asked; `out` is allocated after it (torch's allocator hands out 512-byte aligned
+        # blocks, and the entry checks the pointer itself). If the entry still declines (PSF_E_UNSUPPORTED: a knob changed in
+        # between, an operand it does not take), the route below runs, the buffer is reused there, and the fallback is counted.
+        w_align = 4 if any(p % 16 for p in (V0c.data_ptr(), *w_ptrs)) else 16
+        chord = offsets is None or tuple(offsets) == tuple(0 if k == 0 else (1 << (k - 1)) % N for k in range(L))
+        if lib.psf_chord_chain_last_supported(B, N, L, C, M, w_align, 1 if use_residual else 0, stride0, 1 if chord else 0):
+            out = torch.empty((B, N, C), dtype=V0c.dtype, device=dev)
+            with torch.cuda.device(dev):
+                rc = lib.psf_chord_chain_last_f32(w_tab, V0c.data_ptr(), out.data_ptr(), M, 1 if use_residual else 0, B, N, L, C,
+                                                  stride0, _lib.offsets_array(offsets), _stream_ptr(dev))
+            if rc != _lib.PSF_E_UNSUPPORTED:
+                _lib.check(rc, "psf_chord_chain_last_f32")
+                return V0c, Ws, [out], (B, N, L, C, stride0)
+            global chain_last_declined
+            chain_last_declined += 1
+            spare = out
+    nbuf = M if keep_all else min(M, 2)
+    bufs = [spare if spare is not None and i == 0 else torch.empty((B, N, C), dtype=V0c.dtype, device=dev) for i in range(nbuf)]
+    outs = [bufs[m % nbuf] for m in range(M)]
     o_tab = (ctypes.c_void_p * M)(*[o.data_ptr() for o in outs])
     with torch.cuda.device(dev):
         fn = getattr(lib, "psf_chord_chain_fwd" + _suffix(V0c))

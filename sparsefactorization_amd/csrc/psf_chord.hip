@@ -23,6 +23,7 @@
 #include "chain_tr_lds.h"
 #include "fwd_chain_lds_bf16.h"
 #include "fwd_chain_lds_launch.h"
+#include "fwd_chain_regs_launch.h"
 #include "fwd_kernels.h"
 #include "fwd_mlp_step_launch.h"
 #include "fwd_window_launch.h"
@@ -1160,6 +1161,34 @@ int describe_args(int64_t B, int64_t N, int32_t L, int64_t C, int32_t elem_bytes
   return PSF_OK;
 }
 
+// The last-result chain of a long f32 sequence in one launch (fwd_chain_regs.h): what psf_chord_chain_last_f32 runs, what
+// psf_chord_chain_last_supported answers and what psf_describe_chain_last prints. `fits`: the kernel covers the call (the
+// entry launches it); `automatic`: the caller should prefer the entry to psf_chord_chain_fwd_f32 — knob chain_fused = 2
+// wherever it fits, chain_fused = 1 where the grid fills its rounds of one workgroup per CU (chain_regs_automatic,
+// fwd_chain_regs_launch.h), chain_fused = 0 never.
+struct ChainLastPlan {
+  bool fits, automatic;
+  int cus;
+};
+// CUs of the calling thread's current device; the MI355X's 256 where no device answers (a host without a GPU)
+int current_cus() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
+    (void)hipGetLastError();  // (not this call's business: the next launch must not find it)
+    return kChainRegsDefaultCus;
+  }
+  return cus;
+}
+ChainLastPlan plan_chain_last(const Tuning& tn, int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, int32_t w_align,
+                              bool use_residual, int64_t v0_batch_stride, bool default_offsets) {
+  ChainLastPlan p{};
+  p.fits = default_offsets && chain_regs_fits(B, N, L, C, M) && w_align >= 16 && w_align % 16 == 0 &&
+           (v0_batch_stride == N * C || (v0_batch_stride == 0 && !use_residual));
+  p.cus = p.fits && tn.chain_fused == 1 ? current_cus() : kChainRegsDefaultCus;
+  p.automatic = p.fits && (tn.chain_fused == 2 || (tn.chain_fused == 1 && chain_regs_automatic(B * (C / 2), p.cus)));
+  return p;
+}
+
 void print_win(char* buf, size_t cap, const char* kernel, const Elem& el, int32_t L, const WinPick& pk) {
   snprintf(buf, cap, "%s<%s,L=%d,TG=%d,R=%d,NT=%d>", kernel, el.name, (int)L, 1 << pk.tgs, pk.rows, pk.nt);
 }
@@ -1292,6 +1321,52 @@ int psf_chord_chain_fwd_bf16(const uint16_t* const* W_steps, const uint16_t* V0,
                              const int64_t* offsets, void* stream) {
   return chain_impl<__bf16>(snapshot(), reinterpret_cast<const __bf16* const*>(W_steps), reinterpret_cast<const __bf16*>(V0),
                             reinterpret_cast<__bf16* const*>(out_steps), M, use_residual, B, N, L, C, v0_batch_stride, offsets, stream);
+}
+
+int psf_chord_chain_last_supported(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, int32_t w_align, int32_t use_residual,
+                                   int64_t v0_batch_stride, int32_t default_offsets) {
+  return plan_chain_last(snapshot(), B, N, L, C, M, w_align, use_residual != 0, v0_batch_stride, default_offsets != 0).automatic ? 1 : 0;
+}
+
+// X_M of the chain in exactly one launch (fwd_chain_regs.h), or PSF_E_UNSUPPORTED: no per-step fallback here
+// (psf_chord_chain_fwd_f32 is that route). The entry runs wherever the kernel fits; psf_chord_chain_last_supported is the
+// automatic rule on top of that.
+int psf_chord_chain_last_f32(const float* const* W_steps, const float* V0, float* out, int32_t M, int32_t use_residual, int64_t B,
+                             int64_t N, int32_t L, int64_t C, int64_t v0_batch_stride, const int64_t* offsets, void* stream) {
+  if (M < 1) return fail(PSF_E_SHAPE, "M must be >= 1");
+  if (!W_steps || !V0 || !out) return fail(PSF_E_NULL, "W_steps, V0 and out must be non-NULL");
+  if (int rc = check_dims(B, N, L, C, v0_batch_stride)) return rc;
+  if (out == V0) return fail(PSF_E_ALIAS, "out aliases V0");
+  // the kernel copies W in 16-byte chunks and moves V0 and out rows in 8-byte pieces (C is a multiple of 4: a 16-byte aligned
+  // base makes every piece aligned); anything less aligned is the per-step route's
+  bool align16 = aligned_to(V0, 16) && aligned_to(out, 16), align4 = aligned_to(V0, sizeof(float)) && aligned_to(out, sizeof(float));
+  for (int m = 0; m < M; ++m) {
+    if (!W_steps[m]) return fail(PSF_E_NULL, "step %d: NULL pointer", m);
+    if (W_steps[m] == out) return fail(PSF_E_ALIAS, "step %d: out aliases W", m);
+    align16 = align16 && aligned_to(W_steps[m], 16);
+    align4 = align4 && aligned_to(W_steps[m], sizeof(float));
+  }
+  if (!align4) return fail(PSF_E_ALIGN, "pointers must be aligned to the element size");
+  const int w_align = align16 ? 16 : 4;
+  Offsets offs, chord;
+  make_offsets(N, L, offsets, &offs);
+  make_offsets(N, L, nullptr, &chord);
+  bool default_offsets = true;
+  for (int k = 0; k < L; ++k) default_offsets = default_offsets && offs.v[k] == chord.v[k];
+  const Tuning tn = snapshot();
+  if (!plan_chain_last(tn, B, N, L, C, M, w_align, use_residual != 0, v0_batch_stride, default_offsets).fits) return PSF_E_UNSUPPORTED;
+  ChainRegsArgs a;  // (B >= 1 here: an empty batch is declined with every other shape the kernel does not cover)
+  for (int m = 0; m < kChainMaxSteps; ++m) a.W[m] = m < M ? W_steps[m] : nullptr;
+  a.V0 = V0;
+  a.out = out;
+  a.v0_bstride = v0_batch_stride;
+  a.M = M;
+  a.C = (int32_t)C;
+  a.pairs = (int32_t)(C / 2);
+  a.xcd_remap = tn.xcd_remap ? 1 : 0;
+  hipError_t e = launch_chain_regs(use_residual != 0, a, (int)B, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(e, "chord_chain_regs launch");
+  return PSF_OK;
 }
 
 int psf_chord_chain_bwd_supported(int64_t N, int32_t L, int64_t C, int32_t M) {
@@ -1484,6 +1559,22 @@ int psf_describe_chain_fwd_dtype(int64_t B, int64_t N, int32_t L, int64_t C, int
   else
     snprintf(buf, cap, "chord_chain_lds_k<%s,L=%d,CC=%d,R=%d> one launch for all %d steps, %d threads, %d workgroup(s) per sequence",
              el.name, (int)L, plan.cc, plan.rows, (int)M, plan.threads, plan.chunks);
+  return PSF_OK;
+}
+
+// What psf_chord_chain_last_f32 does with a chain of aligned operands, a full-batch V0 and the chord offsets.
+int psf_describe_chain_last(int64_t B, int64_t N, int32_t L, int64_t C, int32_t M, char* buf, int32_t cap) {
+  if (int rc = describe_args(B, N, L, C, 4, false, buf, cap)) return rc;
+  const ChainLastPlan p = plan_chain_last(snapshot(), B, N, L, C, M, 16, true, N * C, true);
+  if (!p.fits) {
+    snprintf(buf, cap, "declined (PSF_E_UNSUPPORTED): chord_chain_regs_k covers f32, N=%d, L=%d, C a multiple of 4, M <= %d", kChainRegsN,
+             kChainRegsLinks, kChainMaxSteps);
+    return PSF_OK;
+  }
+  using Cfg = ChainRegsCfg<kChainRegsLinks, kChainRegsThreads>;
+  snprintf(buf, cap, "chord_chain_regs_k<f32,L=%d,T=%d,J=%d> one launch for all %d steps, X in registers, W through %d LDS slots of %d bytes, "
+           "%d workgroup(s) per sequence, %s", (int)L, kChainRegsThreads, kChainRegsBlocks, (int)M, Cfg::kSlots, Cfg::kSlotBytes, (int)(C / 2),
+           p.automatic ? "automatic" : "on request only");
   return PSF_OK;
 }
 

@@ -186,6 +186,13 @@ __device__ __forceinline__ void lds_wait_all() { asm volatile("s_waitcnt lgkmcnt
 // front of a workgroup barrier for it (mlp_fwd_bf16.hip: dma_wait): every wave drains its own pieces before the barrier that
 // publishes the image; behind the barrier all pieces have landed.
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// The counted wait of an LDS-DMA ring, in front of the barrier that publishes its oldest stage: all but this wave's N youngest
+// vector-memory operations have completed (they retire in issue order), and all of its LDS operations (its ds_writes are
+// visible behind the barrier, its ds_reads of the stage about to be refilled have returned).
+template <int N>
+__device__ __forceinline__ void dma_wait_all_but() {
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
 __device__ __forceinline__ void behind_wait(float& r) { asm volatile("" : "+v"(r)); }
 __device__ __forceinline__ void behind_wait(float __attribute__((ext_vector_type(4))) & r) { asm volatile("" : "+v"(r)); }
 template <int VEC>
